@@ -22,11 +22,17 @@ explicit exception (N <= 6 ranks share the visible GPUs over gloo: a functional 
   --mode shard-video  BASELINE.json configs[3]: ONE long video, its memory ROWS sharded over the ranks
                       (distributed.RowShardedMemory), per-step all-gather of the new memory (strong scaling).
 
-Timing (contract in the task description): W warm-up steps, then blocks of EXACTLY K steps, each bracketed by a
-barrier + torch.cuda.synchronize() on both sides, MAX over ranks per block.  The block is repeated (>= 5 times and
-until >= ~2 s of timed GPU work) and `value` / `ms_per_step` are those of the MEDIAN block; min / max and the shader
-clock sampled during the blocks are reported beside it.  Rank 0 prints ONE JSON line with `roofline` (dominant kernel,
-measured live with HIP events in a second, instrumented pass of the same K steps) and `cpu_baseline` (N=1 only).
+Timing (contract in the task description): W warm-up steps, then ONE block of EXACTLY K timed steps, bracketed by a
+barrier + torch.cuda.synchronize() on both sides, MAX over ranks; `ms_per_step` = block time / K.  `--repeats R` /
+`--min-seconds S` opt into more blocks (R x K timed steps or more; `value` / `ms_per_step` are then those of the MEDIAN
+block, min / max beside it).  The shader clock sampled during the blocks is reported too.  Rank 0 prints ONE JSON line
+with `roofline` (dominant kernel, measured live with HIP events in a second, instrumented pass of the same K steps) and
+`cpu_baseline` (N=1 only).
+
+`--dump-outputs DIR` (rank 0): after the timed steps, what the timed path handed its caller in the LAST timed step is
+written as DIR/<name>.npy in float32 (replica: each video's token block; shard-video: the memory FIFO and the last chunk's
+frame scores), at most DUMP_BYTES in all - an array over its share is cut to a fixed, seeded sample of its rows.  Inputs
+and weights are seeded, so the same arguments give the same inputs in every run: two builds compare output for output.
 """
 import argparse
 import ctypes
@@ -58,9 +64,10 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mode", choices=("replica", "shard-video"), default="replica")
-    ap.add_argument("--repeats", type=int, default=5, help="minimum number of timed K-step blocks")
-    ap.add_argument("--min-seconds", type=float, default=8.0,
-                    help="keep repeating blocks until this much timed work (>= 8 s: a utilisation sampler sees the GPU busy)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="minimum number of timed K-step blocks (default 1: exactly --steps timed steps)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="keep repeating blocks until this much timed work (default 0: no extra blocks)")
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="functional rehearsal: ranks may share GPUs and talk over gloo (never a measurement)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -76,6 +83,8 @@ def parse_args(argv=None):
     ap.add_argument("--m8-extra", action="store_true", help="also time the reference-default M=8 shape (extras)")
     ap.add_argument("--no-latency", action="store_true",
                     help="skip the single-video latency leg (profiling runs: keeps other launch shapes out of the kernel statistics)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, <= 64 MB in all; rank 0)")
     return ap.parse_args(argv)
 
 
@@ -226,7 +235,7 @@ class ClockSampler:
 
 def timed_blocks(step, sync, args, world, device):
     """W warm-up steps, then >= args.repeats blocks of EXACTLY K steps (barrier + synchronize on both sides of each
-    block, MAX over ranks).  Returns the sorted list of block times in seconds."""
+    block, MAX over ranks; by default one block).  Returns the list of block times in seconds."""
     import torch
     import torch.distributed as dist
 
@@ -251,6 +260,42 @@ def timed_blocks(step, sync, args, world, device):
     for _ in range(n - 1):
         times.append(block())
     return times
+
+
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: all files together, .npy headers included
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """`arrays` (name -> tensor) -> out_dir/<name>.npy in float32, DUMP_BYTES in all.  Smallest first, each array may use an
+    even split of what is left of the budget; one larger than that is viewed as rows of its last dimension and cut to a
+    sample of them (the same seeded, sorted row indices in every run with the same arguments).  Returns
+    {name: {"shape", "rows_kept", "rows"}} for the result line."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    left, share = DUMP_BYTES, None
+    written = {}
+    for n, name in enumerate(sorted(arrays, key=lambda k: arrays[k].numel())):
+        t = arrays[name].detach()
+        # 4 KiB of each file's allowance is kept for the .npy header; once one array is sampled, every larger one gets the
+        # same share (equal arrays: the same rows)
+        fair = share or left // (len(arrays) - n) - 4096
+        rows_all = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(-1, 1)
+        rows, row_bytes = rows_all.shape[0], rows_all.shape[1] * 4
+        if rows * row_bytes <= fair:
+            a = t.float().cpu().numpy()
+        else:
+            share = fair
+            keep = share // row_bytes
+            if keep < 1:
+                raise ValueError(f"--dump-outputs: one row of {name} ({row_bytes} bytes) exceeds its share of the budget")
+            idx = np.sort(np.random.RandomState(DUMP_SEED).choice(rows, keep, replace=False))
+            a = rows_all.index_select(0, torch.from_numpy(idx).to(t.device)).float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        left -= a.nbytes + 4096
+        written[name] = {"shape": list(t.shape), "rows_kept": int(a.reshape(-1, rows_all.shape[1]).shape[0]), "rows": rows}
+    return written
 
 
 def usable_cpus():
@@ -378,6 +423,7 @@ def run_replica(args, rank, world, local, device, dist_info):
     pending = [None]
     do_gather = world > 1 and not args.no_gather
     last = [None]
+    last_outs = [None]      # every video's token block of the last timed step (what pool.run hands its caller)
 
     def final_memory():
         """newest memory of this rank's first video (what the north-star's all-gather ships)"""
@@ -393,7 +439,8 @@ def run_replica(args, rank, world, local, device, dist_info):
         elif single:
             toks = pool1.run([(xi, idx_cpu) for xi in xs[:NB]], mp, fp, model.image_newline)[0]
         else:
-            toks = pool.run([(xi, idx_cpu) for xi in xs], mp, fp, model.image_newline)[0]
+            last_outs[0] = pool.run([(xi, idx_cpu) for xi in xs], mp, fp, model.image_newline)
+            toks = last_outs[0][0]
         if do_gather and not single and not one_video:
             if pending[0] is not None:
                 pending[0].wait()                       # previous gather (overlapped with this step) is done with `send`
@@ -413,6 +460,9 @@ def run_replica(args, rank, world, local, device, dist_info):
     with torch.no_grad(), ClockSampler(device.index) as clk:
         times = timed_blocks(step, sync, args, world, device)
     toks = last[0]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {f"tokens_video{b}": t for b, t in enumerate(last_outs[0])})
     rows_expected = 10 + 2 * MEM_TOKENS * PATCHES + 1 + 9 + 32 * PATCHES + 1
     assert toks.shape == (rows_expected, HIDDEN) and bool(torch.isfinite(toks.float()).all())
     if do_gather:       # every rank's final memory arrived: slot r of the gather equals what rank r sent
@@ -528,6 +578,8 @@ def run_replica(args, rank, world, local, device, dist_info):
         "kernels": kernels,
         "fused_layernorm_exchange": ln_status or None,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     out.update(extras)
     return out
 
@@ -685,8 +737,8 @@ def run_shard_video(args, rank, world, local, device, dist_info):
         sh.reset()
         for i in range(0, T, 32):
             # the next chunk's K/V projection overlaps the all-gather of this step's memory rows
-            cache, _ = sh.step(xp[i:i + 32], prefetch=xp[i + 32:i + 64] if i + 32 < T else None)
-        last[0] = cache
+            cache, scores = sh.step(xp[i:i + 32], prefetch=xp[i + 32:i + 64] if i + 32 < T else None)
+        last[0] = (cache, scores)
         return cache
 
     def sync():
@@ -696,7 +748,12 @@ def run_shard_video(args, rank, world, local, device, dist_info):
 
     with torch.no_grad(), ClockSampler(device.index) as clk:
         times = timed_blocks(step, sync, args, world, device)
-    cache = last[0]
+    cache, scores = last[0]
+    dumped = None
+    if args.dump_outputs and rank == 0:      # the FIFO entries are ring views: written before anything else steps
+        arrays = {f"memory{i}": m for i, m in enumerate(cache)}
+        arrays["frame_scores_last_chunk"] = scores
+        dumped = dump_outputs(args.dump_outputs, arrays)
     assert len(cache) == min(10, -(-T // 32)) and bool(torch.isfinite(torch.stack(list(cache)).float()).all())
     if world > 1:       # every rank ends with the identical FIFO
         chk = torch.stack([c.float().sum() for c in cache])
@@ -709,7 +766,7 @@ def run_shard_video(args, rank, world, local, device, dist_info):
     ts = sorted(times)
     med = ts[len(ts) // 2]
     fl = algorithmic_flops(M=M, frames=T, D=Dh) - 16.0 * (min(T // 32, 10) * M * PATCHES) * Dh * Dh   # no fuser in this loop
-    return {
+    res = {
         "metric": "Memory-Fuser frames/sec, ONE long video with memory rows sharded over the GPUs (configs[3])",
         "value": round(args.steps * T / med, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(med / args.steps * 1e3, 4), "higher_is_better": True,
@@ -727,6 +784,9 @@ def run_shard_video(args, rank, world, local, device, dist_info):
                      "traffic": None, "note": "whole sharded step per GPU (algorithmic flop of the video / ranks / time); the "
                                               "chunk K/V projection is computed redundantly on every rank and not counted twice"},
     }
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    return res
 
 
 def main():

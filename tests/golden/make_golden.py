@@ -163,6 +163,21 @@ def g4():
          table1024_rows=pe1024[[0, 1, 2, 299, 599]], table1024_sum=np.array(pe1024.astype(np.float64).sum()))
 
 
+def g4_cnr():
+    """The sinusoidal table once more, with MKL held to its COMPATIBLE code path (MKL_CBWR, Conditional Numerical
+    Reproducibility): torch's float exp / sin / cos go through MKL's vector math, whose last bit depends on the CPU's code
+    path (g4_pe.npz holds this host's); the COMPATIBLE path gives the same bits on any x86 CPU, so the product's table can
+    be pinned bit for bit on every machine.  MKL reads the variable when it starts: a child process of its own."""
+    if os.environ.get("MKL_CBWR") != "COMPATIBLE":
+        import subprocess
+        subprocess.run([sys.executable, os.path.abspath(__file__), "g4cnr"], env=dict(os.environ, MKL_CBWR="COMPATIBLE"),
+                       check=True)
+        return
+    D = 64
+    table = PEm.TemporalPositionalEncoding(max_frames=600, embed_dim=D, learnable=False).frame_embed.numpy()
+    save("g4_pe_cnr.npz", meta=meta(D=D, max_frames=600, mkl_cbwr="COMPATIBLE"), table=table)
+
+
 # --------------------------------------------------------------------------- glue import
 def import_glue():
     import transformers.modeling_utils as mu
@@ -497,7 +512,7 @@ def g9():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g3", "g4", "g56", "g7", "g7fifo", "g7wide", "g8", "g9"]
+    which = sys.argv[1:] or ["g1", "g3", "g4", "g4cnr", "g56", "g7", "g7fifo", "g7wide", "g8", "g9"]
     if "g9" in which:
         g9()
     if "g8" in which:
@@ -510,6 +525,8 @@ if __name__ == "__main__":
         g3()
     if "g4" in which:
         g4()
+    if "g4cnr" in which:
+        g4_cnr()
     if "g56" in which:
         g5_g6()
     if "g7" in which:

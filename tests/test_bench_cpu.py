@@ -1,5 +1,6 @@
-"""CPU: bench.py's launcher refuses to run fewer ranks than asked (no GPU in this container: every N>1 request must exit
-non-zero with a message), and the timed CPU-baseline code path equals the validated numpy oracle."""
+"""CPU: bench.py's launcher refuses to run fewer ranks than asked (no GPU visible to it: every N>1 request must exit
+non-zero with a message), and the timed CPU-baseline code path equals the validated numpy oracle.  The bench runs with
+HIP_VISIBLE_DEVICES=-1, so it sees no GPU on a machine that has one as well."""
 import os
 import subprocess
 import sys
@@ -14,6 +15,7 @@ def _run(args, env=None):
     e = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         e.pop(k, None)
+    e["HIP_VISIBLE_DEVICES"] = "-1"          # no device, whatever the machine has (takes precedence over ROCR_VISIBLE_DEVICES)
     e.update(env or {})
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=e, capture_output=True, text=True,
                           timeout=300)
@@ -34,7 +36,8 @@ def test_launcher_and_flag_disagree_fails_loudly():
 
 def test_rehearsal_needs_a_gpu_too():
     r = _run(["--gpus", "2", "--rehearse-gloo"])
-    assert r.returncode != 0
+    assert r.returncode != 0 and "no GPU visible" in (r.stderr + r.stdout)
+    assert '"n_gpus"' not in r.stdout
 
 
 def test_cpu_baseline_code_path_equals_the_oracle():

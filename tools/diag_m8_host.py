@@ -1,6 +1,6 @@
 import os, sys, time
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 dev = torch.device("cuda", 0)
 if os.environ.get("BIG_FIRST"):

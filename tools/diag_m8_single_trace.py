@@ -1,7 +1,7 @@
 """Diagnostic (GPU box): 30 single videos at the checkpoint shape (M = 8, D = 1024, 64 frames), one stream - run it under
 `rocprofv3 --kernel-trace --stats` to see the kernel sequence of ONE video (HISTORY R4.9).  usage: rocprofv3 ... -- python3 tools/diag_m8_single_trace.py"""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 dev = torch.device("cuda", 0); torch.cuda.set_device(dev)
 model, arch = bench.build_model(dev, hidden=1024, mem_tokens=8, seed=4321)

@@ -1,5 +1,5 @@
 import os, sys, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import memory_augmented_vlm_amd
 from memory_augmented_vlm_amd import _ops as ops
 R, S, H, D = 12544, 6272, 8, 1024
