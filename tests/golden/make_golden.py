@@ -23,6 +23,20 @@ os.environ.setdefault("PYTHONDONTWRITEBYTECODE", "1")
 os.environ.setdefault("HF_HUB_OFFLINE", "1")
 sys.dont_write_bytecode = True
 
+# g7wide64 pins the CPU numerics so that its fixture does not depend on how the host picks its kernels: at M = 64 the
+# reference's GEMMs are large enough that MKL's blocking (chosen from the ISA and cache sizes) changes the summation order.
+# MKL conditional numerical reproducibility (AVX2 code path, STRICT), ATen's vector kernels at AVX2, oneDNN's (bf16) kernels
+# capped at AVX512_CORE_BF16, 8 threads whatever the environment asks.  It must be set before torch loads MKL, and it would
+# change the other fixtures' bits, so g7wide64 runs on its own.
+PINNED = "g7wide64" in sys.argv[1:]
+if PINNED:
+    if sys.argv[1:] != ["g7wide64"]:
+        sys.exit("make_golden.py: run g7wide64 on its own (it pins the CPU numerics for the whole process)")
+    os.environ["MKL_CBWR"] = "AVX2,STRICT"
+    os.environ["OMP_NUM_THREADS"] = os.environ["MKL_NUM_THREADS"] = "8"
+    os.environ["ATEN_CPU_CAPABILITY"] = "avx2"
+    os.environ["ONEDNN_MAX_CPU_ISA"] = "AVX512_CORE_BF16"
+
 import numpy as np
 import torch
 
@@ -402,6 +416,37 @@ def g7_wide():
     save("g7_wide_fullsize.npz", meta=meta(hidden=3584, wseed=73, segseed0=7300, stride=997, frames=list(G7_WIDE_FRAMES)), **res)
 
 
+G7_WIDE64_CASES = (("m64_", 64, (8, 32), 74, 7400), ("m8_", 8, (32, 32), 75, 7500))   # prefix, M, frames, weight seed, seg seed
+
+
+def g7_wide64():
+    """The OneVision-7B width at the BASELINE's 64 memory tokens (hidden 3584, 8 heads of 448, depth 2), next to the checkpoint's 8:
+    `m64_`: chunks of 8 then 32 frames - step 1 is evolution over the FIFO plus formation on S = 6272 keys, R = 12544 query rows
+    (the stream-K schedule of the wide-head forward, the M = 64 GEMM shapes); `m8_`: two 32-frame chunks (the single-video split-KV
+    grid).  Per case and step, as the G7 fixtures: strided samples + norm of the new memory and the frame scores of the reference's
+    fp32 run, the samples of its bf16 run."""
+    assert PINNED
+    torch.set_num_threads(8)
+    res = {}
+    for pfx, M, frames, wseed, sseed in G7_WIDE64_CASES:
+        cfg = O.PathConfig(hidden=3584, heads=8, mem_tokens=M, depth=2)
+        w = O.make_weights(cfg, seed=wseed)
+        for dtype, sfx in ((torch.float32, ""), (torch.bfloat16, "_refbf16")):
+            m = ref_projector(cfg, w, dtype)
+            m.memory_cache = []
+            m.frame_attn_scores = []
+            for t, F in enumerate(frames):
+                seg = O.bf16_round(O.hash_normal_like((F, 196, 3584), sseed + t))
+                cache, scores = m(T(seg).to(dtype))
+                mem = cache[-1].float().numpy().reshape(-1)
+                res[f"{pfx}s{t}_sample{sfx}"] = mem[::997].copy()
+                if not sfx:
+                    res[f"{pfx}s{t}_norm"] = np.array(np.linalg.norm(mem.astype(np.float64)))
+                    res[f"{pfx}s{t}_scores"] = scores[-1].numpy().copy()
+    cases = {pfx: {"M": M, "frames": list(frames), "wseed": wseed, "segseed0": sseed} for pfx, M, frames, wseed, sseed in G7_WIDE64_CASES}
+    save("g7_wide64_fullsize.npz", meta=meta(hidden=3584, stride=997, cases=cases), **res)
+
+
 # --------------------------------------------------------------------------- G8 (gradients, SURVEY.md §8f rank 3)
 G8_CASES = {"d256": (256, 7), "d1024": (1024, 61)}      # hidden (8 heads: the reference's dead reshape needs H = M = 8), stride
 G8_WIDE = {"d3584": (3584, 1999)}                       # the OneVision-7B width (heads of 448; `python make_golden.py g8wide`, ~1 h of CPU)
@@ -533,5 +578,7 @@ if __name__ == "__main__":
         g7()
     if "g7wide" in which:
         g7_wide()
+    if "g7wide64" in which:
+        g7_wide64()
     if "g7fifo" in which:
         g7_fifo()

@@ -30,3 +30,93 @@ def load_oracle_weights(module_root, w: dict, prefix_map=None):
             sd[k].copy_(torch.from_numpy(np.ascontiguousarray(v)))
             used += 1
     return used
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Gates against a float64 reference, per unit of work rather than per tensor.  A kernel that is wrong in one 128-row unit out of
+# hundreds (a dropped key piece, a misweighted merge) moves a global rel-L2 by little; a per-block rel-L2 sees it.  Every threshold
+# is a multiple of a FLOOR computed from the same data: the rel-L2 that an exact result pays for its rounding to the kernel's
+# output grid (or, for the backward, for the 16-bit rounding points the kernels document).  Work on torch tensors of any device;
+# numpy arrays are taken as well (CPU self-test, tests/test_gates_cpu.py).
+ATTN_UNIT, ATTN_WHOLE, LSE2_ATOL = 2.0, 1.5, 1e-4    # forward: per (128-query unit, head), whole tensor, lse2 per row (abs)
+GEMM_TILE, GEMM_F32_TILE = 2.0, 2e-5                  # GEMM: 16-bit outputs per 256 x 256 tile (x floor), fp32 outputs (rel-L2)
+BWD_BLOCK = 1.5                                       # backward: per (64-row block, head) against the 16-bit-rounding floor
+
+
+def f64(a):
+    """torch float64 view of a tensor (same device) or numpy array (CPU)."""
+    if isinstance(a, torch.Tensor):
+        return a.detach().to(torch.float64)
+    return torch.from_numpy(np.asarray(a, dtype=np.float64))
+
+
+def round_to(x, mode):
+    """float64 -> the 16-bit grid of `mode` ("bf16" / "fp16", round to nearest even) -> float64."""
+    return f64(x).to(DT[mode]).to(torch.float64)
+
+
+def _block_sq(x, rows, cols):
+    R, C = x.shape
+    nr, nc = -(-R // rows), -(-C // cols)
+    x = torch.nn.functional.pad(x, (0, nc * cols - C, 0, nr * rows - R))
+    return x.square().view(nr, rows, nc, cols).sum(dim=(1, 3))
+
+
+def block_rel_l2(got, ref, rows, cols):
+    """rel-L2 of `got` against `ref` per (rows x cols) block of 2-D operands (ragged edge blocks included): [nR, nC] float64.
+    A block whose reference is zero counts its error against 1e-300 (zero only if `got` is zero there too)."""
+    ref = f64(ref)
+    d = f64(got).to(ref.device) - ref
+    return torch.sqrt(_block_sq(d, rows, cols) / _block_sq(ref, rows, cols).clamp_min(1e-300))
+
+
+def rel_l2_t(got, ref):
+    ref = f64(ref)
+    return float(torch.linalg.vector_norm(f64(got).to(ref.device) - ref) / torch.linalg.vector_norm(ref).clamp_min(1e-300))
+
+
+class Gate:
+    """Result of a floor gate: error / floor per block (`worst`, at block `where`) and over the whole tensor (`whole`)."""
+
+    def __init__(self, name, worst, where, whole, floor, unit, whole_max):
+        self.name, self.worst, self.where, self.whole, self.floor = name, worst, where, whole, floor
+        self.ok = worst <= unit and (whole_max is None or whole <= whole_max)
+        self.limits = (unit, whole_max)
+
+    def __str__(self):
+        return (f"{self.name}: worst block {self.worst:.3f} x floor at {self.where}, whole tensor {self.whole:.3f} x floor "
+                f"(floor {self.floor:.2e}; limits {self.limits[0]} / {self.limits[1]})")
+
+
+def floor_gate(name, got, ref, rows, cols, floor, unit, whole_max=None):
+    """err(got) / err(floor) per (rows x cols) block and over the whole tensor, both against `ref` (float64).  `floor`: a 16-bit
+    mode ("bf16" / "fp16": the floor is ref rounded to that grid) or a tensor (a reference with the kernel's rounding points)."""
+    ref = f64(ref)
+    fl = round_to(ref, floor) if isinstance(floor, str) else f64(floor).to(ref.device)
+    e, f = block_rel_l2(got, ref, rows, cols), block_rel_l2(fl, ref, rows, cols)
+    ratio = torch.where(f > 0, e / f.clamp_min(1e-300), torch.where(e > 0, torch.full_like(e, float("inf")), torch.zeros_like(e)))
+    i = int(torch.argmax(ratio))
+    gf = rel_l2_t(fl, ref)
+    ge = rel_l2_t(got, ref)
+    whole = ge / gf if gf > 0 else (0.0 if ge == 0 else float("inf"))
+    return Gate(name, float(ratio.view(-1)[i]), divmod(i, ratio.shape[1]), whole, gf, unit, whole_max)
+
+
+def attention_gate(ctx, lse2, ref_ctx, ref_lse2, heads, mode):
+    """Forward attention: ctx within ATTN_UNIT x floor per (128-query unit, head) and ATTN_WHOLE x floor over the tensor; lse2
+    (log2 domain, [H, R]) within LSE2_ATOL of the reference on every row.  Returns (gate, worst lse2 error, passed)."""
+    ref_ctx = f64(ref_ctx)
+    g = floor_gate("ctx", ctx, ref_ctx, 128, ref_ctx.shape[1] // heads, mode, ATTN_UNIT, ATTN_WHOLE)
+    ref_lse2 = f64(ref_lse2)
+    lerr = float((f64(lse2).to(ref_lse2.device) - ref_lse2).abs().max())
+    return g, lerr, g.ok and lerr <= LSE2_ATOL
+
+
+def gemm_gate(out, ref, mode=None):
+    """GEMM output per 256 x 256 tile: 16-bit outputs (mode "bf16" / "fp16") within GEMM_TILE x floor; fp32 outputs (mode None)
+    within GEMM_F32_TILE rel-L2.  Returns (worst ratio or rel-L2, passed)."""
+    if mode is not None:
+        g = floor_gate("gemm", out, ref, 256, 256, mode, GEMM_TILE)
+        return g.worst, g.ok
+    worst = float(block_rel_l2(out, ref, 256, 256).max())
+    return worst, worst <= GEMM_F32_TILE

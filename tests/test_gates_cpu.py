@@ -1,0 +1,90 @@
+"""CPU: the per-unit floor gates of tests/gpu_util.py (used by test_gpu_ov7b_width.py) reject the errors a wrong kernel makes and
+accept a correctly rounded result.  Reduced shapes, numpy float64 references; the "kernel outputs" are that reference with one
+realistic defect planted: a stream-K unit that drops one of its 16 key pieces, one unit whose merge weight is off by 2^-6, one
+row's log-sum-exp off by 2e-4, one GEMM tile whose contraction stops short."""
+import math
+
+import numpy as np
+
+from oracle import memory_path as O
+from gpu_util import attention_gate, gemm_gate
+
+R, S, H, HD = 8192, 512, 2, 64         # 64 128-query units per head; a unit's keys in 16 pieces of 32
+PIECES = 16
+
+
+def _inputs():
+    q = O.bf16_round(O.hash_normal_like((R, H * HD), 11)).astype(np.float64)
+    k = O.bf16_round(O.hash_normal_like((S, H * HD), 12)).astype(np.float64)
+    v = O.bf16_round(O.hash_normal_like((S, H * HD), 13)).astype(np.float64)
+    return q, k, v
+
+
+def _attention64(q, k, v, keys=slice(None)):
+    """ctx [rows, H*HD], lse2 [H, rows] (log2 domain) in float64 over the key subset `keys`."""
+    ctx = np.empty((q.shape[0], H * HD))
+    lse2 = np.empty((H, q.shape[0]))
+    for h in range(H):
+        sl = slice(h * HD, (h + 1) * HD)
+        s = q[:, sl] @ k[keys, sl].T / math.sqrt(HD)
+        m = s.max(axis=1, keepdims=True)
+        p = np.exp(s - m)
+        l = p.sum(axis=1, keepdims=True)
+        ctx[:, sl] = (p @ v[keys, sl]) / l
+        lse2[h] = (m[:, 0] + np.log(l[:, 0])) / math.log(2.0)
+    return ctx, lse2
+
+
+def _ok(ctx, lse2, ref, ref_lse2, whole=None):
+    g, lerr, ok = attention_gate(ctx, lse2, ref, ref_lse2, H, "bf16")
+    print(g, f"lse2 {lerr:.1e}")
+    if whole is not None:
+        whole.append(g.whole)
+    return ok
+
+
+def test_attention_gate_accepts_the_rounded_reference():
+    ref, lse2 = _attention64(*_inputs())
+    assert _ok(O.bf16_round(ref.astype(np.float32)), lse2.astype(np.float32), ref, lse2)
+
+
+def test_attention_gate_rejects_a_unit_missing_one_key_piece():
+    q, k, v = _inputs()
+    ref, lse2 = _attention64(q, k, v)
+    keep = np.ones(S, bool)
+    keep[5 * S // PIECES:6 * S // PIECES] = False             # unit (rows 128..255, head 1) loses piece 5 of 16
+    c, l = _attention64(q[128:256], k, v, keep)
+    bad, bad_lse = ref.copy(), lse2.copy()
+    bad[128:256, HD:] = c[:, HD:]
+    bad_lse[1, 128:256] = l[1]
+    assert not _ok(O.bf16_round(bad.astype(np.float32)), bad_lse.astype(np.float32), ref, lse2)
+    assert not _ok(O.bf16_round(bad.astype(np.float32)), lse2.astype(np.float32), ref, lse2)    # the context alone
+
+
+def test_attention_gate_rejects_a_misweighted_unit():
+    ref, lse2 = _attention64(*_inputs())
+    bad = ref.copy()
+    bad[:128, HD:] *= 1.0 + 2.0 ** -6
+    whole = []
+    assert not _ok(O.bf16_round(bad.astype(np.float32)), lse2.astype(np.float32), ref, lse2, whole)
+    assert whole[0] < 1.5              # one unit in 128: the whole-tensor gate alone would let it through
+
+
+def test_attention_gate_rejects_one_row_of_lse2():
+    ref, lse2 = _attention64(*_inputs())
+    bad = lse2.copy()
+    bad[0, 77] += 2e-4
+    assert not _ok(O.bf16_round(ref.astype(np.float32)), bad.astype(np.float32), ref, lse2)
+
+
+def test_gemm_tile_gate():
+    M, N, K = 512, 768, 1024
+    a = O.bf16_round(O.hash_normal_like((M, K), 21)).astype(np.float64)
+    w = O.bf16_round(O.hash_normal_like((N, K), 22)).astype(np.float64)
+    ref = a @ w.T
+    bad = ref.copy()
+    bad[256:512, 256:512] = a[256:512, :K - 32] @ w[256:512, :K - 32].T      # one tile's K range stops 32 short
+    assert gemm_gate(O.bf16_round(ref.astype(np.float32)), ref, "bf16")[1]
+    assert not gemm_gate(O.bf16_round(bad.astype(np.float32)), ref, "bf16")[1]
+    assert gemm_gate(ref.astype(np.float32), ref)[1]                                 # fp32 epilogue
+    assert not gemm_gate(bad.astype(np.float32), ref)[1]
