@@ -120,7 +120,9 @@ int mavlm_create(const mavlm_config* cfg, mavlm_ctx** out);
 void mavlm_destroy(mavlm_ctx* ctx);
 size_t mavlm_workspace_bytes(const mavlm_config* cfg);
 /* byte offsets of the 10 workspace regions {kv_seg, q, ctx, a, h, pre(fp32), mA, mB, lse2, colsum_part}: lets the
- * parity tests read the intermediates of the last sub-layer after a step (stage-wise checks) */
+ * parity tests read the intermediates of the last sub-layer after a step (stage-wise checks).  n >= 12 adds entries 10-11 =
+ * {offset, bytes} of the split-K scratch the GEMMs of a step share (on the step's stream); n >= 14 adds entries 12-13 = {offset,
+ * bytes} of the separate split-K scratch of mavlm_project_chunk[_ahead] (0 bytes where no chunk projection splits). */
 int mavlm_workspace_layout(const mavlm_config* cfg, size_t* offsets, int32_t n);
 int mavlm_bind_weights(mavlm_ctx* ctx, const mavlm_weights* w);
 /* (the exchange scratch of the fused Residual kernel inside the workspace is zero-filled by the library itself: an
@@ -170,7 +172,10 @@ int mavlm_project_chunk(mavlm_ctx* ctx, const void* seg, int32_t F, void* stream
  * stream, and the projection of chunk t + 1 - the largest GEMM of a step at few memory tokens - runs beside step t's small-grid
  * kernels (round 4).  The library keeps two chunk K/V buffers (single videos) and orders the streams with events: the projection
  * waits for the last step that read its buffer, the consuming step waits for the projection; nothing to synchronise for the host.
- * Not inside a graph capture (MAVLM_E_STATE).  `seg` must stay valid until the consuming step has been enqueued. */
+ * A projection that splits its contraction does so in a scratch of its own, never in the one of the step it overlaps (same
+ * plan, same bits as the step's inline projection).  Not inside a graph capture (MAVLM_E_STATE).  `seg` must stay valid until
+ * the consuming step has been enqueued.  A discarded projection may still be running: the next eager mavlm_step that writes its
+ * buffer waits for it, a step inside a graph capture that would write it returns MAVLM_E_STATE (run one eager step first). */
 int mavlm_project_chunk_ahead(mavlm_ctx* ctx, const void* seg, int32_t F, void* stream);
 /* number of mavlm_step calls of this context that found (and used) a projection left by mavlm_project_chunk[_ahead] */
 int mavlm_prefetch_hits(const mavlm_ctx* ctx);

@@ -29,6 +29,7 @@ struct mavlm_ctx {
     bool pending = false;          // a projection into this buffer may still be in flight on `stream` (ev_pre not waited for yet)
   } pre[2];
   size_t o_kv2 = 0;                // second chunk K/V buffer (0 = none: row batches)
+  size_t o_kvsplit = 0, kvsplit_floats = 0;   // split-K scratch of the projections made ahead (project_for), never shared with a step
   hipEvent_t ev_pre[2] = {nullptr, nullptr};    // recorded behind a projection into buffer b
   hipEvent_t ev_done[2] = {nullptr, nullptr};   // recorded behind the last step that read buffer b
   bool done_rec[2] = {false, false};
@@ -92,6 +93,26 @@ inline int fuse_mems_per_launch(const mavlm_config& c) {
   return k > c.cache_cap ? c.cache_cap : k;
 }
 
+// floats of the split-K planes of the GEMMs with few output tiles and a long contraction (mavlm_gemm_splits): the I -> D
+// projections (MLP down, fuser second layer) at small R - the scratch o_gsplit every GEMM of a step shares (on the step's stream)
+size_t gemm_split_floats(const mavlm_config& c) {
+  const size_t B = (size_t)nbatch(c);
+  const size_t R1 = (size_t)q_tokens(c) * c.patches, R = (size_t)c.mem_tokens * c.patches * B;
+  const int sk = c.max_chunk_frames * c.patches, d = c.hidden, dp = padded_width(c), in = c.inter, l2 = 2 * c.depth * dp;
+  size_t fl = 0;
+  const int rows_[2] = {(int)R, (int)(R1 * B)};              // every row of the memory / the rows of a row shard
+  for (int r : rows_) {
+    const size_t need[] = {mavlm_gemm_split_ws_floats(r, dp, d, MAVLM_EPI_BIAS, dp),      // q projection
+                           mavlm_gemm_split_ws_floats(r, d, dp, MAVLM_EPI_F32, d),        // attention out dense
+                           mavlm_gemm_split_ws_floats(r, in, d, MAVLM_EPI_RELU, in),      // MLP up / fuser first
+                           mavlm_gemm_split_ws_floats(r, d, in, MAVLM_EPI_F32, d),        // MLP down / fuser second
+                           mavlm_gemm_split_ws_floats(sk, l2, d, MAVLM_EPI_BIAS, l2),     // chunk K/V
+                           mavlm_gemm_split_ws_floats(r, 2 * dp, d, MAVLM_EPI_BIAS, 2 * dp)};   // evolution K/V
+    for (size_t n : need) fl = n > fl ? n : fl;
+  }
+  return fl;
+}
+
 void carve(mavlm_ctx* x) {
   const mavlm_config& c = x->cfg;
   const size_t B = (size_t)nbatch(c);
@@ -103,7 +124,20 @@ void carve(mavlm_ctx* x) {
   size_t o = 0;
   x->o_kv = o;   o += al(B * S * 2 * L * Dp * 2);
   x->o_kv2 = 0;
-  if (B == 1) { x->o_kv2 = o; o += al(S * 2 * L * Dp * 2); }      // landing zone of mavlm_project_chunk_ahead
+  x->o_kvsplit = x->kvsplit_floats = 0;
+  x->gsplit_floats = gemm_split_floats(c);
+  if (B == 1) {
+    x->o_kv2 = o; o += al(S * 2 * L * Dp * 2);      // landing zone of mavlm_project_chunk_ahead
+    // A projection made ahead runs on another stream than the step it overlaps, so it cannot borrow the step's split-K scratch
+    // (o_gsplit: the planes of the step's own small-grid GEMMs).  It gets one of its own, sized for the plan the inline projection
+    // takes (gemm_x: split where the plan fits the step's scratch) at every chunk size up to max_chunk_frames - same plan, same bits.
+    const int l2 = (int)(2 * L * Dp);
+    for (int f = 1; f <= c.max_chunk_frames; ++f) {
+      const size_t need = mavlm_gemm_split_ws_floats(f * c.patches, l2, (int)D, MAVLM_EPI_BIAS, l2);
+      if (need <= x->gsplit_floats && need > x->kvsplit_floats) x->kvsplit_floats = need;
+    }
+    if (x->kvsplit_floats) { x->o_kvsplit = o; o += al(x->kvsplit_floats * 4); }
+  }
   x->o_q = o;    o += al(R * Dp * 2);
   x->o_ctx = o;  o += al(R * Dp * 2);
   x->o_a = o;    o += al(R * D * 2);
@@ -147,23 +181,8 @@ void carve(mavlm_ctx* x) {
     x->split_floats = fl;
     if (fl) o += al(fl * 4);
   }
-  // split-K planes of the GEMMs with few output tiles and a long contraction (mavlm_gemm_splits): the I -> D
-  // projections (MLP down, fuser second layer) at small R
+  // split-K planes of the step's GEMMs (gemm_split_floats)
   x->o_gsplit = o;
-  {
-    x->gsplit_floats = 0;
-    const int rows_[2] = {(int)R, (int)(R1 * B)};              // every row of the memory / the rows of a row shard
-    for (int r : rows_) {
-      const int sk = (int)S, d = (int)D, dp = (int)Dp, in = (int)I, l2 = (int)(2 * L * Dp);
-      const size_t need[] = {mavlm_gemm_split_ws_floats(r, dp, d, MAVLM_EPI_BIAS, dp),      // q projection
-                             mavlm_gemm_split_ws_floats(r, d, dp, MAVLM_EPI_F32, d),        // attention out dense
-                             mavlm_gemm_split_ws_floats(r, in, d, MAVLM_EPI_RELU, in),      // MLP up / fuser first
-                             mavlm_gemm_split_ws_floats(r, d, in, MAVLM_EPI_F32, d),        // MLP down / fuser second
-                             mavlm_gemm_split_ws_floats(sk, l2, d, MAVLM_EPI_BIAS, l2),     // chunk K/V
-                             mavlm_gemm_split_ws_floats(r, 2 * dp, d, MAVLM_EPI_BIAS, 2 * dp)};   // evolution K/V
-      for (size_t n : need) x->gsplit_floats = n > x->gsplit_floats ? n : x->gsplit_floats;
-    }
-  }
   o += al(x->gsplit_floats * 4);
   // scratch of the frame-score variant of the last formation layer's forward (attention3.hip): (a, m) per (head, memory
   // row, frame) and the partial frame sums per (unit, 32-query group)
@@ -424,7 +443,10 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
         x->pre[b].seg = nullptr;
       }
     if (!pre) rb = (x->pre[0].seg && x->pre[0].step > x->steps && x->o_kv2) ? 1 : 0;
-    if (x->pre[rb].pending && !capturing) {
+    if (x->pre[rb].pending) {
+      // a projection into this buffer may still be running on its stream (one that was discarded, or left behind by an error):
+      // an eager step waits for it; a captured one cannot (the event belongs to work outside the graph) - run an eager step first
+      if (capturing) return MAVLM_E_STATE;
       if (x->pre[rb].stream != (void*)s || !pre) MAVLM_TRY(hipStreamWaitEvent(s, x->ev_pre[rb], 0));
       x->pre[rb].pending = false;
     }
@@ -634,8 +656,9 @@ int mavlm_workspace_layout(const mavlm_config* cfg, size_t* offsets, int32_t n) 
   mavlm_ctx t;
   t.cfg = *cfg;
   carve(&t);
-  const size_t o[10] = {t.o_kv, t.o_q, t.o_ctx, t.o_a, t.o_h, t.o_pre, t.o_mA, t.o_mB, t.o_lse, t.o_part};
-  for (int i = 0; i < 10; ++i) offsets[i] = o[i];
+  const size_t o[14] = {t.o_kv, t.o_q, t.o_ctx, t.o_a, t.o_h, t.o_pre, t.o_mA, t.o_mB, t.o_lse, t.o_part,
+                        t.o_gsplit, t.gsplit_floats * 4, t.o_kvsplit, t.kvsplit_floats * 4};
+  for (int i = 0; i < (n < 14 ? n : 14); ++i) offsets[i] = o[i];
   return 0;
 }
 
@@ -756,7 +779,15 @@ int project_for(mavlm_ctx* x, const void* seg, int32_t F, void* stream, int for_
   if (x->pre[tb].pending && x->pre[tb].stream != stream) MAVLM_TRY(hipStreamWaitEvent(s, x->ev_pre[tb], 0));   // an older projection
   if (x->done_rec[tb]) MAVLM_TRY(hipStreamWaitEvent(s, x->ev_done[tb], 0));     // the last step that read this buffer has finished
   const int D = c.hidden, Dp = padded_width(c), ldkv = 2 * c.depth * Dp, S = F * c.patches;
-  MAVLM_TRY(gemm_x(x, s, seg, D, x->w.w_kv_seg, D, x->w.b_kv_seg, ws(x, tb ? x->o_kv2 : x->o_kv), ldkv, S, ldkv, D, MAVLM_EPI_BIAS));
+  // The plan of the inline projection (gemm_x: split-K where the plan fits the step's scratch), on the projections' own scratch:
+  // the step this projection overlaps uses o_gsplit on its stream.  A projection into the other buffer on another stream shares
+  // this scratch: wait for it.
+  const size_t need = mavlm_gemm_split_ws_floats(S, ldkv, D, MAVLM_EPI_BIAS, ldkv);
+  const bool split = need > 0 && need <= x->gsplit_floats;
+  if (split && need > x->kvsplit_floats) return MAVLM_E_STATE;      // (carve covers every chunk size up to max_chunk_frames)
+  if (split && x->pre[1 - tb].pending && x->pre[1 - tb].stream != stream) MAVLM_TRY(hipStreamWaitEvent(s, x->ev_pre[1 - tb], 0));
+  MAVLM_TRY(gemm(c.dtype, s, seg, D, x->w.w_kv_seg, D, x->w.b_kv_seg, ws(x, tb ? x->o_kv2 : x->o_kv), ldkv, S, ldkv, D, MAVLM_EPI_BIAS,
+                 nullptr, 0, split ? (float*)ws(x, x->o_kvsplit) : nullptr, split ? x->kvsplit_floats : 0));
   MAVLM_TRY(hipEventRecord(x->ev_pre[tb], s));
   x->pre[tb].seg = seg;
   x->pre[tb].F = F;

@@ -393,7 +393,15 @@ class GraphedVideoMemory:
     usage:  g = GraphedVideoMemory(model, T=256, frame_idx_cpu=idx)        # captures on the current device
             tokens = g(frames, mem_prompt, frame_prompt, newline)          # copies into the static inputs, replays
     The returned tensor is the graph's static output buffer (valid until the next call).  A new shape (T, indices,
-    with_frames) needs a new instance."""
+    with_frames) needs a new instance.
+
+    A graph replays the device pointers it was captured with: the engine's workspace and FIFO ring, its packed weight copies
+    (fp32 biases / LayerNorm affines, concatenated K/V weights), the PE table, the fuser and token-type parameters.  The instance
+    holds the engine and its packed copies, so those stay allocated while it lives, and before every replay it runs on the host
+    (no device sync) the staleness check an eager video start runs: a weight update (in place, `load_state_dict`, through `.data`
+    after a `train()` phase), `bind_fuser`, `.to()` / `.half()` of the module, or an engine re-created for a longer chunk makes
+    `__call__` raise MavlmError naming what changed instead of replaying.  Build a new instance then (`enable_memory_graphs` does
+    so by itself)."""
 
     @torch.no_grad()
     def __init__(self, model, T: int, frame_idx_cpu: torch.Tensor, with_frames: bool = True, slot=None):
@@ -408,7 +416,8 @@ class GraphedVideoMemory:
         self.mp = torch.zeros((len(MEMORY_PROMPT_IDS), D), device=dev, dtype=dt)
         self.fp = torch.zeros((len(FRAME_PROMPT_IDS), D), device=dev, dtype=dt)
         self.nl = torch.zeros((D,), device=dev, dtype=dt)
-        # warm-up outside capture: engine creation, weight packing, kernel attribute calls, index uploads
+        # warm-up outside capture: engine creation, weight packing, kernel attribute calls, index uploads.  Its eager steps also
+        # wait for (and clear) a K/V projection left pending by a discarded `project_ahead`, which a captured step would refuse.
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -422,9 +431,49 @@ class GraphedVideoMemory:
         # replayed forward is the replayed video's cache, as after an eager forward (matters when the slot is the model itself)
         rm_ = self.view.recurrent_memory_transformer
         self._cache = list(rm_.memory_cache)
+        # what the graph reads: held (the captured pointers stay allocated) and compared before every replay (stale())
+        self._dev, self._dt = dev, dt
+        self._engine = rm_._engine
+        self._keep = self._engine.keep
+        self._version = self._engine.version
+        self._epoch = rm_._packed_epoch
+        self._ptrs = self._outside_ptrs()
+        # (and the device index vectors it reads: _INDEX_CACHE may drop its references to them)
+        self._idx_dev = (_device_indices(self.idx, dev), _device_indices(fine_frame_indices(T), dev))
+
+    def _outside_ptrs(self):
+        """pointers of the tensors the graph reads beside the engine: the PE table, the fuser and token-type parameters"""
+        v = self.view
+        return (v.positional_encoding.table().data_ptr(),) + tuple(
+            p.data_ptr() for m in (v.memory_fuser, v.token_type_embedding) for p in m.parameters())
+
+    def stale(self) -> Optional[str]:
+        """None if a replay computes what an eager video would, else what changed since the capture.  Host only: the
+        staleness protocol of an eager video start (`memory_cache = []`, then `engine()`: re-packs what changed), then a
+        comparison with what the graph was captured with."""
+        rm = self.view.recurrent_memory_transformer
+        p = next(rm.parameters())
+        if p.dtype != self._dt or p.device != self._dev:
+            return "the module was cast to another dtype or moved"
+        if rm._engine is not None and rm._weights_maybe_stale():
+            rm._engine.version = None
+        eng = rm.engine(self._dev, self._dt)
+        if eng is not self._engine:
+            return "the engine was re-created (module moved / cast, or a longer chunk)"
+        if eng.keep is not self._keep or eng.version != self._version or rm._packed_epoch != self._epoch:
+            return "the weights were re-packed (parameter update, load_state_dict, train() phase or bind_fuser)"
+        if self._outside_ptrs() != self._ptrs:
+            return "the PE table, memory_fuser or token_type_embedding tensors were replaced"
+        return None
 
     @torch.no_grad()
     def __call__(self, frames, memory_prompt_embeds, frame_prompt_embeds, image_newline):
+        why = self.stale()
+        if why is not None:
+            raise capi.MavlmError(f"GraphedVideoMemory: stale graph, not replayed: {why} since the capture - build a new one")
+        return self._replay(frames, memory_prompt_embeds, frame_prompt_embeds, image_newline)
+
+    def _replay(self, frames, memory_prompt_embeds, frame_prompt_embeds, image_newline):
         self.x.copy_(frames)
         self.mp.copy_(memory_prompt_embeds)
         self.fp.copy_(frame_prompt_embeds)
@@ -555,7 +604,9 @@ class LlavaMetaForCausalLM:
         """Inference: serve videos of a shape seen before ((frames, frame indices, with_frames) of the sampled video) by replaying
         a captured hipGraph of the whole per-video launch sequence (`GraphedVideoMemory` on the model's own engine: PE add,
         every chunk step, fuser + emit) instead of ~45 launches; the first occurrence of a shape runs eagerly, the second
-        captures.  Bit-identical to the eager path (`test_graph_capture_replay_bit_identical`).  `capacity` graphs are kept
+        captures.  Bit-identical to the eager path (`test_graph_capture_replay_bit_identical`); a graph captured over weights or an
+        engine that have changed since is dropped and captured again (`GraphedVideoMemory.stale`, tests/test_gpu_replay_coherence.py).
+        Training-mode modules run eagerly.  `capacity` graphs are kept
         (least recently used out); 0 switches the cache off.  Each graph holds static copies of its input frames and of its
         token block."""
         self._mem_graph_capacity = int(capacity)
@@ -566,10 +617,12 @@ class LlavaMetaForCausalLM:
         """video_memory_tokens, through the graph cache when it applies (inference, shape seen before)"""
         cap = getattr(self, "_mem_graph_capacity", 0)
         if (cap <= 0 or path_wants_grad(model, mem_prompt, frame_prompt, getattr(model, "image_newline", None))
-                or torch.cuda.is_current_stream_capturing()):
+                or torch.cuda.is_current_stream_capturing() or model.recurrent_memory_transformer.training):
             return video_memory_tokens(model, pooled, idx_cpu, mem_prompt, frame_prompt, model.image_newline, with_frames, out=out)[0]
         key = (pooled.shape[0], tuple(int(i) for i in idx_cpu.tolist()), bool(with_frames), pooled.dtype, pooled.device.index)
         g = self._mem_graphs.pop(key, None)
+        if g is not None and g.stale() is not None:
+            g = None                                       # captured over state that has changed since: dropped, re-captured
         if g is None:
             n = self._mem_graph_seen.get(key, 0) + 1
             self._mem_graph_seen[key] = n
@@ -583,7 +636,8 @@ class LlavaMetaForCausalLM:
             while len(self._mem_graphs) >= cap:
                 self._mem_graphs.pop(next(iter(self._mem_graphs)))
         self._mem_graphs[key] = g                          # (re-inserted last: most recently used)
-        tokens = g(pooled, mem_prompt, frame_prompt, model.image_newline)
+        with torch.no_grad():
+            tokens = g._replay(pooled, mem_prompt, frame_prompt, model.image_newline)     # (validated above / just captured)
         if out is not None:
             out.copy_(tokens)
             return out

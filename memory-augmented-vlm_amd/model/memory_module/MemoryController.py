@@ -549,8 +549,11 @@ class TransformerProjector(nn.Module):
         x = image_features.contiguous()
         scores = torch.empty(F, device=x.device, dtype=x.dtype) if self.compute_frame_scores else None
         lib = capi.lib()
-        capi.check(lib.mavlm_step(eng.ctx, x.data_ptr(), F, scores.data_ptr() if scores is not None else 0, 0,
-                                  ops.stream_ptr()), "mavlm_step")
+        rc = lib.mavlm_step(eng.ctx, x.data_ptr(), F, scores.data_ptr() if scores is not None else 0, 0, ops.stream_ptr())
+        if rc == capi.E_STATE and torch.cuda.is_current_stream_capturing():
+            raise capi.MavlmError("mavlm_step inside a graph capture: the step needs an eager step first (a K/V projection of "
+                                  "`project_ahead` still pending in its buffer, or the first fused step of a new workspace)")
+        capi.check(rc, "mavlm_step")
         self._memory_cache.append(eng.mem_ring[lib.mavlm_newest_slot(eng.ctx)])      # :152
         cap = eng.c.cache_cap
         if len(self._memory_cache) > cap:                                            # :153-154

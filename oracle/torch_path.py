@@ -57,12 +57,12 @@ def layer(m, seg, p, prefix, heads, eps):
 
 def run_steps(p, cfg, segs: List[np.ndarray], cache_cap: int = 10) -> List[torch.Tensor]:
     """TransformerProjector.forward over the chunks of one video (MemoryController.py:118-158): returns the final
-    memory_cache (graph-carrying tensors [M,P,D], oldest first)."""
+    memory_cache (graph-carrying tensors [M,P,D], oldest first).  `segs`: numpy arrays, or tensors on the device of `p`."""
     dt = p[f"{PFX}.initial_memory"].dtype
     R, D = cfg.mem_rows, cfg.hidden
     cache: List[torch.Tensor] = []
     for seg in segs:
-        x = torch.from_numpy(np.ascontiguousarray(seg)).to(dt).reshape(-1, D)
+        x = (seg if isinstance(seg, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(seg))).to(dt).reshape(-1, D)
         if cache:
             m = mha(cache[-1].reshape(R, D), torch.cat(cache, dim=0).reshape(-1, D), p,
                     f"{PFX}.memory_update_attention", cfg.heads, cfg.eps)

@@ -291,3 +291,33 @@ def test_non_video_inputs_behave_as_the_reference_does():
         lm.prepare_inputs_labels_for_multimodal(ids, None, None, None, None, [images, images], modalities=["video", "video"])
     # decode steps / no images: the early exit (:392-394)
     assert lm.prepare_inputs_labels_for_multimodal(ids[:, :1], None, None, None, None, images)[4] is None
+
+
+def test_projection_ahead_has_a_split_scratch_of_its_own(built_lib):
+    """At hidden 3584 with 8 memory tokens and depth 1 (where `ahead_ok()` turns the side-stream projection on by itself) a
+    1-frame chunk's K/V GEMM splits its contraction (196 x 7168 x 3584: 3 planes), and so does the MLP-down of the step it
+    overlaps (1568 x 3584 x 14336, fp32 epilogue: 2 planes).  The projection made ahead must not use the step's split scratch:
+    the workspace carves one of its own (mavlm_workspace_layout entries 12-13), disjoint from the step's (entries 10-11), big
+    enough for the inline projection's plan at every chunk size - so both take the same plan (same bits)."""
+    lib = capi.lib()
+    kv1 = lib.mavlm_linear_ws_floats(196, 7168, 3584, capi.EPI_BIAS, 7168)
+    down = lib.mavlm_linear_ws_floats(1568, 3584, 14336, capi.EPI_F32, 3584)
+    assert kv1 == 3 * 196 * 7168 and down == 2 * 1568 * 3584
+    for depth, splits in ((1, True), (2, False)):
+        c = capi.Config(hidden=3584, heads=8, patches=196, mem_tokens=8, depth=depth, inter=14336, cache_cap=10,
+                        max_chunk_frames=32, dtype=0, eps=1e-12)
+        total = lib.mavlm_workspace_bytes(c)
+        o = (ctypes.c_size_t * 14)(*([7] * 14))
+        assert lib.mavlm_workspace_layout(c, o, 14) == 0
+        gs, gs_bytes, ks, ks_bytes = o[10], o[11], o[12], o[13]
+        assert gs_bytes >= 4 * down and gs + gs_bytes <= total
+        l2 = 2 * depth * 3584
+        needs = [lib.mavlm_linear_ws_floats(f * 196, l2, 3584, capi.EPI_BIAS, l2) for f in range(1, 33)]
+        inline = [n for n in needs if 0 < n <= gs_bytes // 4]          # chunk sizes whose inline projection splits
+        assert bool(inline) == splits and (kv1 in inline) == splits
+        assert ks_bytes == 4 * max(inline, default=0)
+        if splits:
+            assert ks + ks_bytes <= total and (ks + ks_bytes <= gs or gs + gs_bytes <= ks)       # disjoint
+        o10 = (ctypes.c_size_t * 12)(*([7] * 12))
+        assert lib.mavlm_workspace_layout(c, o10, 10) == 0
+        assert list(o10)[:10] == list(o)[:10] and list(o10)[10:] == [7, 7]              # n = 10: the first ten entries only
