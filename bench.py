@@ -7,7 +7,12 @@ One "step" = one pass of the hot path over synthetic 64-frame videos resident in
   formation) incl. frame scores -> Memory-Fuser MLP + token-type add + fine frames + concat into one token block.
 Vision tower and LLM are outside the path.
 
-    python bench.py --gpus N --steps K --warmup W [--mode replica|shard-video]
+    python bench.py --gpus N --steps K --warmup W [--mode replica|shard-video] [--full]
+
+A plain run does only what its headline needs: set up, warm up, time the K steps, dump the outputs if asked, print the
+line.  `--full` (off by default) adds everything else, each part with its own runs after the timed block: the
+instrumented per-kernel pass (`roofline`, `kernels`), the single-video latency, the M = 8 and OV-7B-width extras and the
+CPU baseline (N = 1).  The timed block is the same in both.
 
 Multi-GPU: one process per GPU over RCCL (`nccl`).  Either the driver launches the ranks (`python -m
 torch.distributed.run ... bench.py --gpus N`: RANK / LOCAL_RANK / WORLD_SIZE are read from the environment) or -
@@ -25,9 +30,9 @@ explicit exception (N <= 6 ranks share the visible GPUs over gloo: a functional 
 Timing (contract in the task description): W warm-up steps, then ONE block of EXACTLY K timed steps, bracketed by a
 barrier + torch.cuda.synchronize() on both sides, MAX over ranks; `ms_per_step` = block time / K.  `--repeats R` /
 `--min-seconds S` opt into more blocks (R x K timed steps or more; `value` / `ms_per_step` are then those of the MEDIAN
-block, min / max beside it).  The shader clock sampled during the blocks is reported too.  Rank 0 prints ONE JSON line
-with `roofline` (dominant kernel, measured live with HIP events in a second, instrumented pass of the same K steps) and
-`cpu_baseline` (N=1 only).
+block, min / max beside it).  The shader clock sampled during the blocks is reported too.  Rank 0 prints ONE JSON line;
+with `--full` it also carries `roofline` (dominant kernel, measured live with HIP events in a second, instrumented pass of
+the same K steps) and `cpu_baseline` (N=1 only).
 
 `--dump-outputs DIR` (rank 0): after the timed steps, what the timed path handed its caller in the LAST timed step is
 written as DIR/<name>.npy in float32 (replica: each video's token block; shard-video: the memory FIFO and the last chunk's
@@ -80,11 +85,15 @@ def parse_args(argv=None):
     ap.add_argument("--shard-frames", type=int, default=1024, help="shard-video: frames of the one long video")
     ap.add_argument("--shard-hidden", type=int, default=3584, help="shard-video: hidden width (3584 = OV-7B)")
     ap.add_argument("--shard-mem-tokens", type=int, default=8)
-    ap.add_argument("--m8-extra", action="store_true", help="also time the reference-default M=8 shape (extras)")
+    ap.add_argument("--m8-extra", action="store_true",
+                    help="with --full: also time the reference-default M=8 shape when N > 1 (N = 1 times it by default)")
     ap.add_argument("--no-latency", action="store_true",
                     help="skip the single-video latency leg (profiling runs: keeps other launch shapes out of the kernel statistics)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's outputs as DIR/<name>.npy (float32, <= 64 MB in all; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need (per-kernel roofline pass, single-video latency, "
+                         "M=8 and OV-7B-width extras, CPU baseline); a plain run stops after the timed steps")
     return ap.parse_args(argv)
 
 
@@ -469,22 +478,23 @@ def run_replica(args, rank, world, local, device, dist_info):
         mine = gathered[rank].float()
         assert bool(torch.isfinite(gathered.float()).all()) and torch.equal(mine, send.float())
 
-    # ---- instrumented pass: the same K steps with a HIP-event pair around every kernel launch, ONE stream (one row batch of
-    # NB videos in flight: kernel durations are not smeared by the other stream)
+    # ---- --full only: the instrumented pass - the same K steps with a HIP-event pair around every kernel launch, ONE stream
+    # (one row batch of NB videos in flight: kernel durations are not smeared by the other stream)
     lib = capi.lib()
-    with torch.no_grad():
-        lib.mavlm_prof_enable(1)
-        for _ in range(args.steps):
-            step(single=True)
-        sync()
-        kernels, ms, ln, fl, by = kernel_table(lib, capi, args.steps)
-        lib.mavlm_prof_enable(0)
-        # single-video latency (one video, one stream, no row batch): what a request waits for.  Its engine is created
-        # here (the pools above run row batches), and the card has just idled through the read-back of the event table:
-        # warm up for ~0.1 s, then the best of 3 blocks of 10
-        single_ms = single_graph_ms = None
-        if not args.no_latency:
-            single_ms, single_graph_ms = single_video_latency(model, arch, x, idx_cpu, device)
+    single_ms = single_graph_ms = None
+    if args.full:
+        with torch.no_grad():
+            lib.mavlm_prof_enable(1)
+            for _ in range(args.steps):
+                step(single=True)
+            sync()
+            kernels, ms, ln, fl, by = kernel_table(lib, capi, args.steps)
+            lib.mavlm_prof_enable(0)
+            # single-video latency (one video, one stream, no row batch): what a request waits for.  Its engine is created
+            # here (the pools above run row batches), and the card has just idled through the read-back of the event table:
+            # warm up for ~0.1 s, then the best of 3 blocks of 10
+            if not args.no_latency:
+                single_ms, single_graph_ms = single_video_latency(model, arch, x, idx_cpu, device)
     # the fused dense + residual + LayerNorm epilogue exchanges row statistics between workgroups with a bounded spin: a
     # timeout (never seen) would mean a wrong result - fail loudly rather than print a number
     ln_status = {}
@@ -496,53 +506,61 @@ def run_replica(args, rank, world, local, device, dist_info):
             ln_status["launches"] = ln_status.get("launches", 0) + st[0]
             ln_status["timeouts"] = ln_status.get("timeouts", 0) + st[1]
     assert ln_status.get("timeouts", 0) == 0, ln_status
-    dom = "attention_fwd"
-    di = capi.KERNEL_KINDS.index(dom)
-    info = (ctypes.c_int32 * 4)()       # which instantiation the plan picks at the formation shape (S = one chunk's keys)
-    capi.check(lib.mavlm_attention_plan(MEM_TOKENS * PATCHES, 32 * PATCHES, HEADS * NB, info), "mavlm_attention_plan")
-    kname = f"attn_fwd3_kernel<BF16, {info[0]}, 0>"
-    mi = capi.KERNEL_KINDS.index("attention_merge")
-    fi = capi.KERNEL_KINDS.index("attention_fwd_frames")
-    knote = ("HIP-event bracket around this kernel only (all its launches of a step: formation and evolution shapes; the last "
-             f"formation layer of a step runs the frame-score variant attn_fwd3_kernel<BF16, {info[0]}, 1> on the SAME schedule - "
-             f"{ms[fi] / max(ln[fi], 1) * 1e3:.1f} us per launch, kernels.attention_fwd_frames - which replaces the "
-             f"column-sum pass); a launch serves the {NB} video(s) of a row batch ({HEADS * NB} (video, head) pairs); "
-             + (f"schedule: levelled stream-K, {info[1]} workgroups of {info[0]} waves, {info[2]} level(s); its merge kernel "
-                f"attn_combine_sk_kernel<BF16> is bracketed separately: {ms[mi] / max(ln[mi], 1) * 1e3:.1f} us per launch "
-                "(kernels.attention_merge)" if info[1] else "plain grid"))
-    achieved = fl[di] / (ms[di] * 1e-3) / 1e12
-    # every attention-forward launch of a step, weighted by time (plain + frame-score variant + merges)
-    att_ms = ms[di] + ms[fi] + ms[mi]
-    att_weighted = (fl[di] + fl[fi]) / (att_ms * 1e-3) / 1e12 if att_ms > 0 else 0.0
-    traffic, tnote = None, None
-    for tp in ("r04_attn_fwd_hbm_traffic.json", "r03_attn_fwd_hbm_traffic.json"):
-        tpath = os.path.join(ROOT, "profiles", tp)
-        if os.path.exists(tpath):      # PMC summary committed from a separate rocprofv3 --pmc run (tools/pmc_traffic.sh)
-            tj = json.load(open(tpath))
-            traffic = tj.get("bench_avg_bytes_per_launch")
-            tnote = (f"NOT measured in this run: constant from profiles/{tp} (separate rocprofv3 --pmc passes over the same "
-                     "command, FETCH_SIZE x2 gfx950 correction + WRITE_SIZE, averaged over this kernel's launches of a step = "
-                     f"its real launch mix: {tj.get('launch_mix', 'see file')}); algorithmic bytes per launch in alg_bytes_per_launch")
-            break
-    roofline = {"bound": "mfma", "achieved": round(achieved, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_note": tnote,
-                "kernel": kname, "kernel_note": knote,
-                "avg_launch_ms": round(ms[di] / ln[di], 5), "launches_per_step": ln[di] / args.steps,
-                "alg_flops_per_launch": fl[di] / ln[di], "alg_bytes_per_launch": by[di] / ln[di],
-                "hbm_gbs_algorithmic": round(by[di] / (ms[di] * 1e-3) / 1e9, 1),
-                "attention_fwd_all_launches_tflops": round(att_weighted, 1),
-                "attention_fwd_all_launches_frac": round(att_weighted / MFMA_PEAK_TFLOPS, 4),
-                "clock_note": "frac is against the nominal 2.5 PFLOP/s (2.4 GHz); sclk of THIS box while the blocks ran: "
-                              "timing.clock; the box profiles/r04_* were taken on: profiles/README.md"}
 
-    extras = {}
-    if args.m8_extra or (world == 1 and os.environ.get("MAVLM_BENCH_M8", "1") != "0"):
-        extras["m8_checkpoint_shape"] = run_m8_extra(args, device, arch)
-    if world == 1 and not args.no_latency and os.environ.get("MAVLM_BENCH_OV7B", "1") != "0":
-        try:
-            extras["ov7b_width_configs2"] = run_ov7b_extra(args, device)
-        except Exception as e:                # an extra never costs the line (e.g. a box short of memory)
-            extras["ov7b_width_configs2"] = {"error": f"{type(e).__name__}: {e}"[:300]}
+    full = {}
+    if args.full:
+        dom = "attention_fwd"
+        di = capi.KERNEL_KINDS.index(dom)
+        info = (ctypes.c_int32 * 4)()       # which instantiation the plan picks at the formation shape (S = one chunk's keys)
+        capi.check(lib.mavlm_attention_plan(MEM_TOKENS * PATCHES, 32 * PATCHES, HEADS * NB, info), "mavlm_attention_plan")
+        kname = f"attn_fwd3_kernel<BF16, {info[0]}, 0>"
+        mi = capi.KERNEL_KINDS.index("attention_merge")
+        fi = capi.KERNEL_KINDS.index("attention_fwd_frames")
+        knote = ("HIP-event bracket around this kernel only (all its launches of a step: formation and evolution shapes; the "
+                 f"last formation layer of a step runs the frame-score variant attn_fwd3_kernel<BF16, {info[0]}, 1> on the SAME "
+                 f"schedule - {ms[fi] / max(ln[fi], 1) * 1e3:.1f} us per launch, kernels.attention_fwd_frames - which replaces "
+                 f"the column-sum pass); a launch serves the {NB} video(s) of a row batch ({HEADS * NB} (video, head) pairs); "
+                 + (f"schedule: levelled stream-K, {info[1]} workgroups of {info[0]} waves, {info[2]} level(s); its merge kernel "
+                    f"attn_combine_sk_kernel<BF16> is bracketed separately: {ms[mi] / max(ln[mi], 1) * 1e3:.1f} us per launch "
+                    "(kernels.attention_merge)" if info[1] else "plain grid"))
+        achieved = fl[di] / (ms[di] * 1e-3) / 1e12
+        # every attention-forward launch of a step, weighted by time (plain + frame-score variant + merges)
+        att_ms = ms[di] + ms[fi] + ms[mi]
+        att_weighted = (fl[di] + fl[fi]) / (att_ms * 1e-3) / 1e12 if att_ms > 0 else 0.0
+        traffic, tnote = None, None
+        for tp in ("r04_attn_fwd_hbm_traffic.json", "r03_attn_fwd_hbm_traffic.json"):
+            tpath = os.path.join(ROOT, "profiles", tp)
+            if os.path.exists(tpath):      # PMC summary committed from a separate rocprofv3 --pmc run (tools/pmc_traffic.sh)
+                tj = json.load(open(tpath))
+                traffic = tj.get("bench_avg_bytes_per_launch")
+                tnote = (f"NOT measured in this run: constant from profiles/{tp} (separate rocprofv3 --pmc passes over the same "
+                         "command, FETCH_SIZE x2 gfx950 correction + WRITE_SIZE, averaged over this kernel's launches of a step "
+                         f"= its real launch mix: {tj.get('launch_mix', 'see file')}); algorithmic bytes per launch in "
+                         "alg_bytes_per_launch")
+                break
+        full["roofline"] = {
+            "bound": "mfma", "achieved": round(achieved, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_note": tnote,
+            "kernel": kname, "kernel_note": knote,
+            "avg_launch_ms": round(ms[di] / ln[di], 5), "launches_per_step": ln[di] / args.steps,
+            "alg_flops_per_launch": fl[di] / ln[di], "alg_bytes_per_launch": by[di] / ln[di],
+            "hbm_gbs_algorithmic": round(by[di] / (ms[di] * 1e-3) / 1e9, 1),
+            "attention_fwd_all_launches_tflops": round(att_weighted, 1),
+            "attention_fwd_all_launches_frac": round(att_weighted / MFMA_PEAK_TFLOPS, 4),
+            "clock_note": "frac is against the nominal 2.5 PFLOP/s (2.4 GHz); sclk of THIS box while the blocks ran: "
+                          "timing.clock; the box profiles/r04_* were taken on: profiles/README.md"}
+        full["single_video_latency_ms"] = round(single_ms, 3) if single_ms is not None else None
+        full["single_video_latency_graph_ms"] = round(single_graph_ms, 3) if single_graph_ms is not None else None
+        full["kernel_timing_note"] = (f"per-kernel numbers from an instrumented pass with ONE stream (a row batch of {NB} "
+                                      "video(s)) in flight")
+        full["kernels"] = kernels
+        if args.m8_extra or (world == 1 and os.environ.get("MAVLM_BENCH_M8", "1") != "0"):
+            full["m8_checkpoint_shape"] = run_m8_extra(args, device, arch)
+        if world == 1 and not args.no_latency and os.environ.get("MAVLM_BENCH_OV7B", "1") != "0":
+            try:
+                full["ov7b_width_configs2"] = run_ov7b_extra(args, device)
+            except Exception as e:                # an extra never costs the line (e.g. a box short of memory)
+                full["ov7b_width_configs2"] = {"error": f"{type(e).__name__}: {e}"[:300]}
 
     if rank != 0:
         return None
@@ -562,25 +580,20 @@ def run_replica(args, rank, world, local, device, dist_info):
                                "rows of a batch are stacked into every weight-shared GEMM / LayerNorm launch)",
                    "frames": FRAMES, "mem_tokens": MEM_TOKENS, "hidden": HIDDEN, "parallelism": f"replica x{world}",
                    "videos_per_step_per_gpu": B, "streams": NS, "row_batch": NB, "allgather_final_memory": bool(do_gather),
-                   "frame_scores": not args.no_frame_scores, "mode": "replica"},
+                   "frame_scores": not args.no_frame_scores, "mode": "replica", "full": bool(args.full)},
         "timing": {"blocks": len(times), "steps_per_block": args.steps, "statistic": "median block",
                    "ms_per_step_min": round(times_sorted[0] / args.steps * 1e3, 4),
                    "ms_per_step_max": round(times_sorted[-1] / args.steps * 1e3, 4),
                    "value_best_block": round(world * args.steps * B * FRAMES / times_sorted[0], 1),
                    "timed_seconds_total": round(sum(times), 3), "clock": clk.summary()},
         "ranks": dist_info,
-        "roofline": roofline,
         "alg_tflop_per_video": round(flops / 1e12, 3),
         "path_mfma_frac": round(B * flops / (med / args.steps) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-        "single_video_latency_ms": round(single_ms, 3) if single_ms is not None else None,
-        "single_video_latency_graph_ms": round(single_graph_ms, 3) if single_graph_ms is not None else None,
-        "kernel_timing_note": f"per-kernel numbers from an instrumented pass with ONE stream (a row batch of {NB} video(s)) in flight",
-        "kernels": kernels,
         "fused_layernorm_exchange": ln_status or None,
     }
     if dumped is not None:
         out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-    out.update(extras)
+    out.update(full)
     return out
 
 
@@ -840,7 +853,7 @@ def main():
     else:
         out = run_replica(args, rank, world, local, device, dist_info)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and args.mode == "replica":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.mode == "replica":
             out["cpu_baseline"] = cpu_baseline()
             out["speedup_vs_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
         print(json.dumps(out), flush=True)

@@ -56,3 +56,10 @@ def test_cpu_baseline_code_path_equals_the_oracle():
     assert O.rel_l2(got, cache[-1]) < 1e-5
     got16 = TP.cpu_reference_step_timer(cfg, w, segs, torch.bfloat16)().float().numpy()
     assert O.rel_l2(got16, cache[-1]) < 3e-2             # the reference's own bf16 envelope
+
+
+def test_full_is_off_by_default():
+    """A plain run times the headline only; the instrumented pass, latency, extras and CPU baseline ask for `--full`."""
+    import bench
+    assert bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    assert bench.parse_args(["--full"]).full is True

@@ -12,7 +12,7 @@ TAG=${1:-r02}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp ATTN_ONLY3=1 MAVLM_BENCH_M8=0
-B="python3 $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --repeats 3 --min-seconds 0"
+B="python3 $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --repeats 3 --min-seconds 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats1 -- $B --videos-in-flight 1 > $OUT/stats1.json 2> $OUT/stats1.err || echo "stats1 failed"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats2 -- $B > $OUT/stats2.json 2> $OUT/stats2.err || echo "stats2 failed"
 for op in attn colsum gemm; do
