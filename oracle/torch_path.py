@@ -17,11 +17,11 @@ import torch
 PFX = "recurrent_memory_transformer"
 
 
-def params_from(w: Dict[str, np.ndarray], dtype=torch.float64) -> Dict[str, torch.Tensor]:
-    """Leaf tensors (requires_grad) for every floating-point entry of the oracle weight dict but the PE buffer."""
+def params_from(w: Dict[str, np.ndarray], dtype=torch.float64, device="cpu") -> Dict[str, torch.Tensor]:
+    """Leaf tensors (requires_grad) for every floating-point entry of the oracle weight dict but the PE buffer, on `device`."""
     out = {}
     for k, v in w.items():
-        t = torch.from_numpy(np.ascontiguousarray(v)).to(dtype)
+        t = torch.from_numpy(np.ascontiguousarray(v)).to(device=device, dtype=dtype)
         if k != "positional_encoding.frame_embed":
             t.requires_grad_(True)
         out[k] = t
@@ -102,5 +102,5 @@ def cpu_reference_step_timer(cfg, w: Dict[str, np.ndarray], segs: List[np.ndarra
 def grads(p: Dict[str, torch.Tensor], loss: torch.Tensor) -> Dict[str, np.ndarray]:
     names = [k for k, t in p.items() if t.requires_grad]
     gs = torch.autograd.grad(loss, [p[k] for k in names], allow_unused=True)
-    return {k: (np.zeros(tuple(p[k].shape), np.float32) if g is None else g.detach().to(torch.float32).numpy())
+    return {k: (np.zeros(tuple(p[k].shape), np.float32) if g is None else g.detach().to(torch.float32).cpu().numpy())
             for k, g in zip(names, gs)}

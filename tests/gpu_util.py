@@ -41,6 +41,7 @@ def load_oracle_weights(module_root, w: dict, prefix_map=None):
 ATTN_UNIT, ATTN_WHOLE, LSE2_ATOL = 2.0, 1.5, 1e-4    # forward: per (128-query unit, head), whole tensor, lse2 per row (abs)
 GEMM_TILE, GEMM_F32_TILE = 2.0, 2e-5                  # GEMM: 16-bit outputs per 256 x 256 tile (x floor), fp32 outputs (rel-L2)
 BWD_BLOCK = 1.5                                       # backward: per (64-row block, head) against the 16-bit-rounding floor
+F32_SUM_BLOCK = 8.0                                   # fp32 sums over rows (dgamma, dbeta, bias grads): per block x fp32 floor
 
 
 def f64(a):
@@ -120,3 +121,52 @@ def gemm_gate(out, ref, mode=None):
         return g.worst, g.ok
     worst = float(block_rel_l2(out, ref, 256, 256).max())
     return worst, worst <= GEMM_F32_TILE
+
+
+def attention_bwd_ref64(q, k, v, do, heads, scale, mode, head_dim, rows=2048, o=None):
+    """Gradients of softmax(q k^T scale) v per head of `head_dim` columns in float64, query-blocked by `rows` (works on the
+    device of the operands): (exact, rounded), each (dq, dk, dv).  `rounded` takes the rounding points the flash-style backward
+    kernels document (attention_bwd.hip, attention_bwd_hd.hip) - the forward output O stored in 16 bits (delta = rowsum(dO o O)),
+    P and dS = P o (dP - delta) rounded to 16 bits as the operands of the second products, the scale on the fp32 result, the
+    gradients stored in 16 bits - and is the floor of the gate.  `o`: the stored forward output the kernels read (default: the
+    exact O rounded to 16 bits).  They differ where the forward's own rounding matters: a nearly one-hot row's O carries the
+    16-bit rounding of its dominant probability (taken relative to a stale row maximum, up to 2^8), coherently over the row,
+    and dP - delta cancels down to that size."""
+    R, S, W = q.shape[0], k.shape[0], heads * head_dim
+    z = lambda n: torch.zeros((n, W), device=q.device, dtype=torch.float64)
+    ex, rd = [z(R), z(S), z(S)], [z(R), z(S), z(S)]
+    rnd = lambda t: round_to(t, mode)
+    for h in range(heads):
+        sl = slice(h * head_dim, (h + 1) * head_dim)
+        kh, vh = k[:, sl].double(), v[:, sl].double()
+        for r0 in range(0, R, rows):
+            qb, dob = q[r0:r0 + rows, sl].double(), do[r0:r0 + rows, sl].double()
+            s = (qb @ kh.T) * scale
+            p = torch.exp(s - torch.logsumexp(s, dim=1, keepdim=True))
+            oe = p @ vh
+            dp = dob @ vh.T
+            ds = p * (dp - (dob * oe).sum(dim=1, keepdim=True))
+            ob = rnd(oe) if o is None else o[r0:r0 + rows, sl].double()
+            ds_r = rnd(p * (dp - (dob * ob).sum(dim=1, keepdim=True)))
+            ex[0][r0:r0 + rows, sl] = (ds @ kh) * scale
+            rd[0][r0:r0 + rows, sl] = (ds_r @ kh) * scale
+            ex[1][:, sl] += (ds.T @ qb) * scale
+            rd[1][:, sl] += ds_r.T @ qb
+            ex[2][:, sl] += p.T @ dob
+            rd[2][:, sl] += rnd(p).T @ dob
+        rd[1][:, sl] *= scale
+    return ex, [rnd(t) for t in rd]
+
+
+def f32_sum_gate(name, got, ref, fp32_result, cols):
+    """fp32 sums over many rows (LayerNorm dgamma / dbeta, bias gradients): rel-L2 of `got` against the float64 `ref` per block
+    of `cols` entries within F32_SUM_BLOCK x an fp32 floor from the same data - per block, the larger of the rel-L2 of a plain
+    torch fp32 evaluation of the same sum (`fp32_result`) and of `ref` rounded to fp32 once."""
+    ref = f64(ref).reshape(1, -1)
+    fl = torch.maximum(block_rel_l2(f64(fp32_result).reshape(1, -1), ref, 1, cols),
+                       block_rel_l2(ref.to(torch.float32), ref, 1, cols))
+    e = block_rel_l2(f64(got).reshape(1, -1), ref, 1, cols)
+    ratio = e / fl.clamp_min(1e-300)
+    i = int(torch.argmax(ratio))
+    return Gate(name, float(ratio.view(-1)[i]), (0, i), rel_l2_t(got, ref.view(-1)) / max(float(fl.max()), 1e-300),
+                float(fl.max()), F32_SUM_BLOCK, None)

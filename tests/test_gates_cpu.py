@@ -1,13 +1,15 @@
 """CPU: the per-unit floor gates of tests/gpu_util.py (used by test_gpu_ov7b_width.py) reject the errors a wrong kernel makes and
 accept a correctly rounded result.  Reduced shapes, numpy float64 references; the "kernel outputs" are that reference with one
 realistic defect planted: a stream-K unit that drops one of its 16 key pieces, one unit whose merge weight is off by 2^-6, one
-row's log-sum-exp off by 2e-4, one GEMM tile whose contraction stops short."""
+row's log-sum-exp off by 2e-4, one GEMM tile whose contraction stops short, a dK missing one 64-row query tile's contribution
+(the backward gate of test_gpu_backward_m64.py), a dW whose last split-K range is dropped or counted twice."""
 import math
 
 import numpy as np
+import torch
 
 from oracle import memory_path as O
-from gpu_util import attention_gate, gemm_gate
+from gpu_util import BWD_BLOCK, attention_bwd_ref64, attention_gate, floor_gate, gemm_gate
 
 R, S, H, HD = 8192, 512, 2, 64         # 64 128-query units per head; a unit's keys in 16 pieces of 32
 PIECES = 16
@@ -88,3 +90,41 @@ def test_gemm_tile_gate():
     assert not gemm_gate(O.bf16_round(bad.astype(np.float32)), ref, "bf16")[1]
     assert gemm_gate(ref.astype(np.float32), ref)[1]                                 # fp32 epilogue
     assert not gemm_gate(bad.astype(np.float32), ref)[1]
+
+
+def test_backward_gate_rejects_a_dk_missing_one_query_tile():
+    """dK = scale * dS^T Q sums over every query row: a kernel that skips one 64-row query tile (e.g. a dropped workgroup
+    of the row loop) leaves every key block short of 1/64 of its terms.  The per-(64-key block, head) gate against the
+    rounded float64 reference rejects it and accepts that reference."""
+    rows, keys, tile = 4096, 256, 64
+    t = lambda a: torch.from_numpy(O.bf16_round(a).astype(np.float64))
+    q, k = t(O.hash_normal_like((rows, H * HD), 31)), t(O.hash_normal_like((keys, H * HD), 32))
+    v, do = t(O.hash_normal_like((keys, H * HD), 33)), t(O.hash_normal_like((rows, H * HD), 34, 0.5))
+    scale = 1.0 / math.sqrt(HD)
+    ex, rd = attention_bwd_ref64(q, k, v, do, H, scale, "bf16", HD, rows=1024)
+    keep = torch.ones(rows, dtype=torch.bool)
+    keep[7 * tile:8 * tile] = False                          # query tile 7 of 64 contributes nothing
+    _, rd_bad = attention_bwd_ref64(q[keep], k, v, do[keep], H, scale, "bf16", HD, rows=1024)
+    ok = floor_gate("dK", rd[1], ex[1], 64, HD, rd[1], BWD_BLOCK)
+    bad = floor_gate("dK", rd_bad[1], ex[1], 64, HD, rd[1], BWD_BLOCK)
+    print(ok, bad, sep="\n")
+    assert ok.ok and not bad.ok
+
+
+def test_tile_gate_rejects_a_dw_with_its_last_split_wrong():
+    """dW = dY^T X over K = 6 272 rows in 8 split-K planes of 832 (the last one 448, as mavlm_launch_gemm_splitk cuts it):
+    a reduction that drops the last plane or adds it twice is rejected by the per-tile gate; the rounded float64 result
+    passes."""
+    m, n, k, ksplit = 512, 512, 6272, 832
+    a = O.bf16_round(O.hash_normal_like((m, k), 41)).astype(np.float64)
+    b = O.bf16_round(O.hash_normal_like((n, k), 42)).astype(np.float64)
+    ref = a @ b.T
+    lo = (k // ksplit) * ksplit
+    assert k - lo == 448
+    last = a[:, lo:] @ b[:, lo:].T
+    assert gemm_gate(O.bf16_round(ref.astype(np.float32)), ref, "bf16")[1]
+    for bad in (ref - last, ref + last):
+        assert not gemm_gate(O.bf16_round(bad.astype(np.float32)), ref, "bf16")[1]
+        one = ref.copy()
+        one[256:, :256] = bad[256:, :256]                   # in one 256 x 256 tile only
+        assert not gemm_gate(O.bf16_round(one.astype(np.float32)), ref, "bf16")[1]

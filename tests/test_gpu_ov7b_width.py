@@ -16,8 +16,8 @@ from memory_augmented_vlm_amd import _capi as capi
 from memory_augmented_vlm_amd import _ops as ops
 from oracle import memory_path as O
 from conftest import load_golden
-from gpu_util import (ATTN_UNIT, ATTN_WHOLE, BWD_BLOCK, DT, attention_gate, floor_gate, gemm_gate, rel_l2_t, round_to, to_dev,
-                      to_np)
+from gpu_util import (ATTN_UNIT, ATTN_WHOLE, BWD_BLOCK, DT, attention_bwd_ref64, attention_gate, floor_gate, gemm_gate, rel_l2_t,
+                      round_to, to_dev, to_np)
 
 pytestmark = pytest.mark.gpu
 D, H, HD, P = 3584, 8, 448, 196
@@ -176,36 +176,6 @@ def test_dense_residual_layernorm_k14336_vs_fp64(fused, request):
 
 
 # ----------------------------------------------------------------------------------------------------------------- backward
-def attention_bwd_ref64(q, k, v, do, heads, scale, mode, rows=2048):
-    """Gradients of softmax(q k^T scale) v in float64: (exact, rounded), each (dq, dk, dv).  `rounded` takes the rounding points
-    attention_bwd_hd.hip documents - the forward output O stored in 16 bits (delta = rowsum(dO o O)), P and dS = P o (dP - delta)
-    rounded to 16 bits as the operands of the second products, the scale on the fp32 result (OB.attention_bwd(...,
-    scale_in_ds=False)), the gradients stored in 16 bits - and is the floor of the gate."""
-    R, S, W = q.shape[0], k.shape[0], heads * HD
-    z = lambda n: torch.zeros((n, W), device=q.device, dtype=torch.float64)
-    ex, rd = [z(R), z(S), z(S)], [z(R), z(S), z(S)]
-    rnd = lambda t: round_to(t, mode)
-    for h in range(heads):
-        sl = slice(h * HD, (h + 1) * HD)
-        kh, vh = k[:, sl].double(), v[:, sl].double()
-        for r0 in range(0, R, rows):
-            qb, dob = q[r0:r0 + rows, sl].double(), do[r0:r0 + rows, sl].double()
-            s = (qb @ kh.T) * scale
-            p = torch.exp(s - torch.logsumexp(s, dim=1, keepdim=True))
-            o = p @ vh
-            dp = dob @ vh.T
-            ds = p * (dp - (dob * o).sum(dim=1, keepdim=True))
-            ds_r = rnd(p * (dp - (dob * rnd(o)).sum(dim=1, keepdim=True)))
-            ex[0][r0:r0 + rows, sl] = (ds @ kh) * scale
-            rd[0][r0:r0 + rows, sl] = (ds_r @ kh) * scale
-            ex[1][:, sl] += (ds.T @ qb) * scale
-            rd[1][:, sl] += ds_r.T @ qb
-            ex[2][:, sl] += p.T @ dob
-            rd[2][:, sl] += rnd(p).T @ dob
-        rd[1][:, sl] *= scale
-    return ex, [rnd(t) for t in rd]
-
-
 # the training path's formation at M = 8 over a 32-frame chunk: R = 8 x 196 query rows, S = 32 x 196 keys; and the M = 64 shape
 @pytest.mark.parametrize("R,S", [(8 * P, 32 * P), (64 * P, 32 * P)], ids=["m8-chunk32", "m64-chunk32"])
 def test_attention_bwd_flash_448_vs_fp64(R, S):
@@ -218,7 +188,7 @@ def test_attention_bwd_flash_448_vs_fp64(R, S):
     scale = ops.attn_scale(HD)
     o, lse = ops.attention(q, k, v, H, want_lse=True, head_dim=HD, scale=scale)
     full = ops.attention_bwd_hd(q, k, v, o, do, lse, H, HD, scale)
-    ex, rd = attention_bwd_ref64(q, k, v, do, H, scale, mode)
+    ex, rd = attention_bwd_ref64(q, k, v, do, H, scale, mode, HD)
     gates = []
     for i, name in enumerate(("dQ", "dK", "dV")):
         g = floor_gate(name, full[i], ex[i], 64, HD, rd[i], BWD_BLOCK)
