@@ -28,7 +28,7 @@ def main():
     model = Model(cfg)
     model.embed_tokens = torch.nn.Embedding(50000, cfg.hidden_size)
     model.image_newline = torch.nn.Parameter(torch.zeros(cfg.hidden_size))
-    model = model.to(dev).to(torch.bfloat16)
+    model = model.to(dev).to(torch.bfloat16).eval()           # (a module left in train() mode re-packs its weights per video)
 
     T = 64                                                     # frames after the reference's sub-sampling
     frames = (torch.randn(T, 196, cfg.hidden_size, device=dev) * 0.5).bfloat16()   # pooled SigLIP tokens [T,196,D]
@@ -73,6 +73,17 @@ def main():
         torch.cuda.synchronize()
         dt8 = (time.perf_counter() - t0) / (20 * len(vids))
     print(f"2 streams x row batch of 8: {dt8 * 1e3:.3f} ms/video ({T / dt8:,.0f} frames/s)")
+
+    # ---- attention maps: which frames did each memory token read? (grouped sums of the probabilities, opt-in) ---------------
+    rm = model.recurrent_memory_transformer
+    rm.record_attention_maps = True
+    with torch.no_grad():
+        arch.video_memory_tokens(model, frames, idx, mp, fp, model.image_newline)
+    m = rm.attention_maps[-1]                                 # the last chunk: formation [depth, H, M, F], evolution [H, M, n_past]
+    top = m.formation[-1].sum(0).argmax(dim=1).tolist()       # per memory token: the frame of the chunk it read most (last layer)
+    print(f"attention maps: formation {tuple(m.formation.shape)}, evolution "
+          f"{tuple(m.evolution.shape) if m.evolution is not None else None}; most-read frame per memory token {top}")
+    rm.record_attention_maps = False
 
     # ---- hipGraph: the whole per-video launch sequence as one graph ---------------------------------------------
     g = arch.GraphedVideoMemory(model, T, idx)

@@ -161,6 +161,20 @@ int mavlm_step(mavlm_ctx* ctx, const void* seg, int32_t F, void* frame_scores, i
  * exact for every row-wise operator, the attention keeps each video on its own keys.  Not bit-identical to B single-video
  * contexts where the attention schedule differs (fp32 summation order of the cut units); same rounding points. */
 int mavlm_step_batch(mavlm_ctx* ctx, const void* const* segs, int32_t F, void* frame_scores, int32_t scores_f32, void* stream);
+/* Attention maps of the steps (off by default).  While a buffer of mavlm_attention_maps_floats(cfg) floats is bound, every
+ * mavlm_step / mavlm_step_batch runs the group-mass pass behind each attention of the step and writes, for video b of the row
+ * batch, at maps + b * V with V = depth*H*M*max_chunk_frames + H*M*cache_cap  (M = mem_tokens, or q_tokens of a row shard):
+ *   + 0:                              formation, every layer: [depth, H, M, F] for the step's F (query group = the `patches`
+ *                                     rows of one memory token, key group = one frame);
+ *   + depth*H*M*max_chunk_frames:     evolution: [H, M, n] over the n = mavlm_cache_len() memories cached BEFORE the step, oldest
+ *                                     first (the order of the reference's torch.cat(self.memory_cache)); untouched by the first
+ *                                     step of a video.
+ * The rest of the buffer is the pass's scratch.  The buffer is the caller's; the workspace and every other output of the step
+ * are the same bits with and without it.  maps = null turns the pass off.  Needs patches % 4 == 0 (MAVLM_E_SHAPE; the floats
+ * query returns 0); too small a buffer -> MAVLM_E_ARG.  A step inside a hipGraph capture while a buffer is bound returns
+ * MAVLM_E_STATE (bind and unbind outside captures; a graph captured without the maps keeps running without them). */
+int64_t mavlm_attention_maps_floats(const mavlm_config* cfg);
+int mavlm_bind_attention_maps(mavlm_ctx* ctx, float* maps, int64_t maps_floats);
 int mavlm_batch(const mavlm_ctx* ctx);      /* B = max(config.batch, 1) */
 /* K/V projection of a chunk ahead of its mavlm_step (the one GEMM of a step that does not read the memory): lets a host
  * overlap it with an exchange the step has to wait for - the all-gather of the previous memory's rows in the row-sharded
@@ -300,6 +314,18 @@ int64_t mavlm_attention_colsum_floats(int32_t R, int32_t S, int32_t H);
 int mavlm_attention_colsum_plan(int32_t R, int32_t S, int32_t H, int32_t info[2]);
 int mavlm_attention_colsum(const void* Q, int32_t ldq, const void* K, int32_t ldk, const float* lse2, float* part,
                            int64_t part_floats, int32_t R, int32_t S, int32_t H, float scale, int32_t dtype, void* stream);
+/* Attention maps: the mass of the normalised probabilities per (head, query group, key group),
+ *   out[h][i][j] = sum over q in query group i, k in key group j of softmax(scale * Q_h K_h^T)[q][k]     fp32,
+ * [H, ceil(R/q_group), ceil(S/k_group)] for groups of q_group consecutive rows and k_group consecutive keys (the last group
+ * of either side may be short).  The grouped readings of the reference's `attn_probs` (MemoryController.py:98-110, 135-139)
+ * without storing the probabilities: a second pass over Q, K and the forward's lse2, deterministic, no atomics.  `out` is
+ * also the pass's scratch (needs no clearing): it must hold mavlm_attention_group_mass_floats() floats, the result is at its
+ * start; fewer -> MAVLM_E_ARG.  head_dim 128 (narrower heads zero-padded to 128 columns) or 448, q_group > 0, k_group > 0 and
+ * k_group % 4 == 0; anything else -> MAVLM_E_SHAPE.  All arguments are checked before anything is enqueued. */
+int64_t mavlm_attention_group_mass_floats(int32_t R, int32_t S, int32_t H, int32_t q_group, int32_t k_group);
+int mavlm_attention_group_mass(const void* Q, int32_t ldq, const void* K, int32_t ldk, const float* lse2, float* out,
+                               int64_t out_floats, int32_t R, int32_t S, int32_t H, int32_t head_dim, float scale,
+                               int32_t q_group, int32_t k_group, int32_t dtype, void* stream);
 /* out = LayerNorm(x fp32 [rows,D] + res) * gamma + beta -> 16-bit; res: 16-bit [rows, ldr] residual or null.
  * MemoryController.py:24,26-28 */
 int mavlm_layernorm(const float* x, const void* res, int32_t ldr, const float* gamma, const float* beta, void* out,

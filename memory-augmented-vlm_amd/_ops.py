@@ -155,6 +155,29 @@ def attention_colsum(q, k, lse2, heads, head_dim=128, wide_kernel=False, scale=N
     return part
 
 
+def attention_group_mass(q, k, lse2, heads, q_group, k_group, head_dim=128, scale=None):
+    """mass[h,i,j] = sum of the softmax probabilities of head h over the rows of query group i (q_group consecutive rows)
+    and the keys of key group j (k_group consecutive keys; k_group % 4 == 0): fp32 [H, ceil(R/q_group), ceil(S/k_group)].
+    The grouped reading of the reference's `attn_probs` without the probabilities; `lse2` is `attention(...)`'s."""
+    _need_gpu(q, k, lse2)
+    R, _, ldq = _rows(q)
+    S, _, ldk = _rows(k)
+    q_group, k_group = int(q_group), int(k_group)
+    if q_group <= 0 or k_group <= 0 or k_group % 4 or head_dim not in (128, 448):
+        raise capi.MavlmError("attention_group_mass: q_group > 0, k_group > 0 and a multiple of 4, head_dim 128 or 448")
+    if tuple(lse2.shape) != (heads, R) or lse2.dtype != torch.float32 or not lse2.is_contiguous():
+        raise capi.MavlmError("attention_group_mass: lse2 must be a contiguous fp32 [heads, R]")
+    lib = capi.lib()
+    nq, nk = -(-R // q_group), -(-S // k_group)
+    buf = torch.empty((int(lib.mavlm_attention_group_mass_floats(R, S, heads, q_group, k_group)),), device=q.device,
+                      dtype=torch.float32)          # result first, the pass's scratch behind it
+    capi.check(lib.mavlm_attention_group_mass(q.data_ptr(), ldq, k.data_ptr(), ldk, lse2.data_ptr(), buf.data_ptr(), buf.numel(),
+                                              R, S, heads, head_dim,
+                                              1.0 / math.sqrt(head_dim) if scale is None else float(scale), q_group, k_group,
+                                              dtype_code(q.dtype), stream_ptr()), "mavlm_attention_group_mass")
+    return buf[:heads * nq * nk].view(heads, nq, nk)
+
+
 def layernorm(x_f32, gamma_f32, beta_f32, eps, out_dtype, out=None, residual=None):
     """out = LayerNorm(x_f32 + residual) * gamma + beta; residual: optional 16-bit [rows, D] (added in fp32)."""
     _need_gpu(x_f32, gamma_f32, beta_f32, residual)

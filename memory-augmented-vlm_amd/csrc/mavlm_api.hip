@@ -43,6 +43,7 @@ struct mavlm_ctx {
   int fuse_mems = 1;   // cached memories the Memory-Fuser MLP takes per GEMM launch (mavlm_fuse_emit)
   int fused_ln = 1;    // snapshot of the process-wide hook at mavlm_create (0 = two-kernel form, 1 / 2 = fused where supported)
   int ln_wide = 0;     // ... and of its "rows of up to 4096 columns" test mode
+  float* maps = nullptr;    // attention maps of every step (mavlm_bind_attention_maps): the caller's buffer, null = off
   bool lnx_clean = false;   // the exchange scratch of this workspace has been zero-filled since the last mavlm_bind_buffers
 };
 
@@ -387,6 +388,34 @@ int step_frames_fused(const mavlm_ctx* x, int S) {
   return mavlm_attention_frames_supported(R1, S, c.heads * B, c.patches) ? 1 : 0;
 }
 
+// ---- attention maps (mavlm_bind_attention_maps): layout of the caller's buffer.  Per video: the formation maps of a step
+// [depth, H, M, F] (compact for the step's F) in a region sized for max_chunk_frames, then the evolution map [H, M, n] in a region
+// sized for cache_cap; behind the last video the scratch of the pass.
+inline size_t maps_form_floats(const mavlm_config& c) { return (size_t)c.depth * c.heads * q_tokens(c) * c.max_chunk_frames; }
+inline size_t maps_video_floats(const mavlm_config& c) { return maps_form_floats(c) + (size_t)c.heads * q_tokens(c) * c.cache_cap; }
+inline bool maps_supported(const mavlm_config& c) { return shape_ok(&c) && c.patches % 4 == 0; }
+size_t maps_floats(const mavlm_config& c) {
+  const int Rq1 = q_tokens(c) * c.patches, R1 = c.mem_tokens * c.patches, P = c.patches, H = c.heads;
+  const size_t f = mavlm_group_mass_floats(Rq1, c.max_chunk_frames * P, H, P, P) - mavlm_group_mass_out_floats(Rq1, c.max_chunk_frames * P, H, P, P);
+  const size_t e = mavlm_group_mass_floats(Rq1, c.cache_cap * R1, H, P, R1) - mavlm_group_mass_out_floats(Rq1, c.cache_cap * R1, H, P, R1);
+  return (size_t)nbatch(c) * maps_video_floats(c) + (f > e ? f : e);
+}
+// the pass behind one attention of the step: Q of the block sits in the workspace (o_q), lse2 in o_lse; one launch pair per video
+int step_maps(mavlm_ctx* x, hipStream_t s, const char* K, int ldk, long long kv_bs, int S, int k_group, int k_rot, size_t out_off) {
+  const mavlm_config& c = x->cfg;
+  const int B = nbatch(c), Rq1 = q_tokens(c) * c.patches, H = c.heads, Dp = padded_width(c);
+  for (int b = 0; b < B; ++b) {
+    mavlm_group_mass_args g;
+    g.Q = ws(x, x->o_q) + (size_t)b * Rq1 * Dp * 2; g.ldq = Dp; g.K = K + (size_t)b * kv_bs * 2; g.ldk = ldk;
+    g.lse2 = (const float*)ws(x, x->o_lse) + (size_t)b * H * Rq1;
+    g.out = x->maps + (size_t)b * maps_video_floats(c) + out_off;
+    g.scratch = x->maps + (size_t)B * maps_video_floats(c);
+    g.R = Rq1; g.S = S; g.H = H; g.scale = attn_scale(c); g.q_group = c.patches; g.k_group = k_group; g.k_rot = k_rot;
+    MAVLM_TRY(mavlm_launch_group_mass(g, wide_heads(c) ? c.hidden / c.heads : 128, c.dtype, s));
+  }
+  return 0;
+}
+
 int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scores, int32_t scores_f32, hipStream_t s) {
   const mavlm_config& c = x->cfg;
   // R1: memory rows of one video (keys of the evolution, ring strides); Rq1: the rows of them this context computes (row
@@ -400,6 +429,12 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
   const int n = x->steps < cap ? x->steps : cap;
   // evolution K/V ring: [B][cap][R1][2 Dp] - the keys of ONE video are contiguous over its slots
   const long long evo_bs = (long long)cap * R1 * 2 * Dp;
+  // attention maps: every attention of the step hands its lse2 to the pass behind it (same O: the forward only stores it too)
+  float* const maps_lse = x->maps ? (float*)ws(x, x->o_lse) : nullptr;
+  if (x->maps) {          // a replayed graph would keep writing the maps of the captured step into the caller's buffer
+    hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cst) != hipSuccess || cst != hipStreamCaptureStatusNone) return MAVLM_E_STATE;
+  }
 
   const void* cur = x->w.mem0;
   if (x->steps > 0) {
@@ -420,8 +455,12 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
     }
     const char* kv = (const char*)x->b.evo_kv_ring;
     int rc = attn_block(x, s, x->w.evo, mem_new + (size_t)r0 * D * 2, kv, 2 * Dp, kv + (size_t)Dp * 2, 2 * Dp, evo_bs, n * R1,
-                        ws(x, x->o_mA), nullptr);
+                        ws(x, x->o_mA), maps_lse);
     if (rc) return rc;
+    if (x->maps) {        // [H, M, n]: key group = one cached memory, oldest first (the ring's oldest slot once it is full)
+      rc = step_maps(x, s, kv, 2 * Dp, evo_bs, n * R1, R1, x->steps > cap ? x->steps % cap : 0, maps_form_floats(c));
+      if (rc) return rc;
+    }
     cur = ws(x, x->o_mA);
   }
 
@@ -463,11 +502,15 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
     const char* Vl = Kl + (size_t)Dp * 2;
     // frame scores: fused into this layer's forward (default), or the column-sum pass over its Q / K / lse2
     const int fused_scores = want_scores ? step_frames_fused(x, S) : 0;
-    float* lse = want_scores ? (float*)ws(x, x->o_lse) : nullptr;      // (the fused form does not need it; kept for inspection)
+    float* lse = want_scores ? (float*)ws(x, x->o_lse) : maps_lse;     // (the fused form does not need it; kept for inspection)
     int frows = 0;
     int rc = attn_block(x, s, x->w.layer_attn[l], cur, Kl, ldkv, Vl, ldkv, (long long)S * ldkv, S, ws(x, x->o_a), lse,
                         fused_scores, &frows);
     if (rc) return rc;
+    if (x->maps) {        // [H, M, F] of layer l: query group = one memory token, key group = one frame
+      rc = step_maps(x, s, Kl, ldkv, (long long)S * ldkv, S, c.patches, 0, (size_t)l * H * q_tokens(c) * F);
+      if (rc) return rc;
+    }
     if (fused_scores) {
       MAVLM_TRY(mavlm_launch_frame_finish((const float*)ws(x, x->o_fout), frows, B, F, c.patches, frame_scores, scores_f32, dt, s));
     } else if (want_scores) {
@@ -1056,6 +1099,40 @@ int mavlm_attention_colsum(const void* Q, int32_t ldq, const void* K, int32_t ld
   a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.lse2 = lse2; a.part = part; a.R = R; a.S = S; a.H = H; a.scale = scale;
   hipError_t e = mavlm_launch_colsum(a, dtype, (hipStream_t)stream);
   return e == hipErrorInvalidValue ? MAVLM_E_ARG : (int)e;
+}
+
+int64_t mavlm_attention_group_mass_floats(int32_t R, int32_t S, int32_t H, int32_t q_group, int32_t k_group) {
+  return (R > 0 && S > 0 && H > 0 && q_group > 0 && k_group > 0) ? (int64_t)mavlm_group_mass_floats(R, S, H, q_group, k_group) : 0;
+}
+
+int mavlm_attention_group_mass(const void* Q, int32_t ldq, const void* K, int32_t ldk, const float* lse2, float* out,
+                               int64_t out_floats, int32_t R, int32_t S, int32_t H, int32_t head_dim, float scale,
+                               int32_t q_group, int32_t k_group, int32_t dtype, void* stream) {
+  // every check comes before any launch
+  if (!Q || !K || !lse2 || !out || R <= 0 || S <= 0 || H <= 0 || (ldq & 7) || (ldk & 7) || (dtype != 0 && dtype != 1))
+    return MAVLM_E_ARG;
+  if (!mavlm_group_mass_supported(R, S, H, head_dim, q_group, k_group)) return MAVLM_E_SHAPE;
+  if (ldq < H * head_dim || ldk < H * head_dim) return MAVLM_E_ARG;
+  if (out_floats < (int64_t)mavlm_group_mass_floats(R, S, H, q_group, k_group)) return MAVLM_E_ARG;
+  mavlm_group_mass_args a;
+  a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.lse2 = lse2; a.out = out;
+  a.scratch = out + mavlm_group_mass_out_floats(R, S, H, q_group, k_group);
+  a.R = R; a.S = S; a.H = H; a.scale = scale; a.q_group = q_group; a.k_group = k_group;
+  hipError_t e = mavlm_launch_group_mass(a, head_dim, dtype, (hipStream_t)stream);
+  return e == hipErrorInvalidValue ? MAVLM_E_ARG : (int)e;
+}
+
+int64_t mavlm_attention_maps_floats(const mavlm_config* cfg) {
+  return (cfg_ok(cfg) && maps_supported(*cfg)) ? (int64_t)maps_floats(*cfg) : 0;
+}
+
+int mavlm_bind_attention_maps(mavlm_ctx* x, float* maps, int64_t maps_floats_) {
+  if (!x) return MAVLM_E_ARG;
+  if (!maps) { x->maps = nullptr; return 0; }
+  if (!maps_supported(x->cfg)) return MAVLM_E_SHAPE;
+  if (maps_floats_ < (int64_t)maps_floats(x->cfg) || ((uintptr_t)maps & 3)) return MAVLM_E_ARG;
+  x->maps = maps;
+  return 0;
 }
 
 int mavlm_layernorm(const float* xin, const void* res, int32_t ldr, const float* gamma, const float* beta, void* out,

@@ -198,6 +198,24 @@ hipError_t mavlm_launch_colsum3(const mavlm_colsum_args& a, int dtype, hipStream
 hipError_t mavlm_launch_attention_hd(const mavlm_attn_args& a, int head_dim, int dtype, hipStream_t s);
 hipError_t mavlm_launch_colsum_hd(const mavlm_colsum_args& a, int head_dim, int dtype, hipStream_t s);
 
+// attention maps (attention_maps.hip): out[h][i][j] = sum over the rows of query group i and the keys of key group j of
+// exp2(s*c - lse2[h][q]); groups of q_group consecutive rows / k_group consecutive keys (k_group % 4 == 0), head_dim 128 or 448
+struct mavlm_group_mass_args {
+  const void* Q; int ldq;
+  const void* K; int ldk;
+  const float* lse2;             // [H, R]
+  float* out;                    // [H, ceil(R/q_group), ceil(S/k_group)]
+  float* scratch;                // mavlm_group_mass_floats() - mavlm_group_mass_out_floats() floats; needs no clearing
+  int R, S, H;
+  float scale;
+  int q_group, k_group;
+  int k_rot = 0;                 // output column j holds key group (j + k_rot) mod groups (a FIFO ring read oldest first)
+};
+bool mavlm_group_mass_supported(int R, int S, int H, int head_dim, int q_group, int k_group);
+size_t mavlm_group_mass_out_floats(int R, int S, int H, int q_group, int k_group);
+size_t mavlm_group_mass_floats(int R, int S, int H, int q_group, int k_group);     // result + scratch
+hipError_t mavlm_launch_group_mass(const mavlm_group_mass_args& a, int head_dim, int dtype, hipStream_t s);
+
 // frame_scores[f] = (1/P) * sum_{p<P} sum_h part[h][f*P+p]     (MemoryController.py:135-139)
 hipError_t mavlm_launch_frame_scores(const float* part, int planes, int H, int S, int F, int P, void* out, int out_f32,
                                      int dtype, hipStream_t s);

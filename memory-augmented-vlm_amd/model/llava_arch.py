@@ -617,7 +617,8 @@ class LlavaMetaForCausalLM:
         """video_memory_tokens, through the graph cache when it applies (inference, shape seen before)"""
         cap = getattr(self, "_mem_graph_capacity", 0)
         if (cap <= 0 or path_wants_grad(model, mem_prompt, frame_prompt, getattr(model, "image_newline", None))
-                or torch.cuda.is_current_stream_capturing() or model.recurrent_memory_transformer.training):
+                or torch.cuda.is_current_stream_capturing() or model.recurrent_memory_transformer.training
+                or getattr(model.recurrent_memory_transformer, "record_attention_maps", False)):      # (maps: eager steps only)
             return video_memory_tokens(model, pooled, idx_cpu, mem_prompt, frame_prompt, model.image_newline, with_frames, out=out)[0]
         key = (pooled.shape[0], tuple(int(i) for i in idx_cpu.tolist()), bool(with_frames), pooled.dtype, pooled.device.index)
         g = self._mem_graphs.pop(key, None)

@@ -14,7 +14,9 @@ wave-reduce LayerNorm.  The sub-modules keep their parameters (so checkpoints lo
 
 Deliberate deviations from the reference (documented in DESIGN.md):
   * `Attention.forward` returns a `FusedAttentionStats` (column sums + log-sum-exp) instead of the
-    materialised probability tensor (MemoryController.py:52,57) - the only consumer reads column sums (:135).
+    materialised probability tensor (MemoryController.py:52,57) - the only consumer reads column sums (:135).  Grouped
+    readings of the probabilities (per frame, per past memory) come from `FusedAttentionStats.group_mass` and, per forward,
+    from `record_attention_maps` (`AttentionMaps`), without ever storing them.
   * the dead per-chunk statistics of the evolution step (:99-109) are not computed, so the reference's implicit
     `num_memory_tokens % 8 == 0` / `heads == 8` requirement (reshape(8,-1,8), :109) does not apply.
   * tensors in the returned `memory_cache` are views into a ring buffer owned by the module: an entry is
@@ -69,6 +71,22 @@ class FusedAttentionStats:
 
     def column_sums(self) -> torch.Tensor:
         return self.column_sums_per_head().sum(dim=0)
+
+    def group_mass(self, q_group: int, k_group: int) -> torch.Tensor:
+        """[H, ceil(R/q_group), ceil(S/k_group)] fp32: the probability mass of every (head, query group, key group) cell -
+        what the reference reads off `attn_probs` per frame or per past memory (MemoryController.py:98-110, 135-139)."""
+        return ops.attention_group_mass(self._q, self._k, self.lse2, self.heads, q_group, k_group)
+
+
+class AttentionMaps:
+    """Attention maps of one `TransformerProjector.forward` (`record_attention_maps`), fp32:
+    formation [depth, H, M, F]: mass of memory token m's `patch_size` query rows on the patches of frame f, per layer and head
+              (`attn_probs` of every formation layer, grouped; summed over H and M and divided by P it is the frame scores);
+    evolution [H, M, n_past] or None on a video's first chunk: mass on each cached memory, oldest first (`attn_chunk_map`).
+    `BatchedProjector` adds a leading video axis to both."""
+
+    def __init__(self, formation, evolution):
+        self.formation, self.evolution = formation, evolution
 
 
 class Residual(nn.Module):
@@ -231,6 +249,39 @@ class _Engine:
         elif rc < 0:
             capi.check(rc, "mavlm_ln_status_async")
 
+    # -- attention maps (include/mavlm.h: mavlm_bind_attention_maps) ----------------------------------------------------------
+    maps = None                       # the bound fp32 buffer (None = the pass is off)
+
+    def set_maps(self, on: bool):
+        """bind / unbind the attention-map buffer of this engine's steps"""
+        if bool(on) == (self.maps is not None):
+            return
+        lib = capi.lib()
+        if on and torch.cuda.is_current_stream_capturing():
+            raise capi.MavlmError("record_attention_maps cannot be turned on inside a graph capture (eager steps write the maps)")
+        if not on:                    # (host-side only: legal anywhere, a step captured afterwards runs without the pass)
+            capi.check(lib.mavlm_bind_attention_maps(self.ctx, 0, 0), "mavlm_bind_attention_maps")
+            self.maps = None
+            return
+        n = int(lib.mavlm_attention_maps_floats(self.c))
+        if n <= 0:
+            raise capi.MavlmError("record_attention_maps: configuration not supported (patch_size must be a multiple of 4)")
+        buf = torch.empty((n,), device=self.device, dtype=torch.float32)
+        capi.check(lib.mavlm_bind_attention_maps(self.ctx, buf.data_ptr(), n), "mavlm_bind_attention_maps")
+        self.maps = buf
+
+    def read_maps(self, F: int, n_past: int):
+        """copies of the maps the last step wrote: (formation [B, depth, H, M, F], evolution [B, H, M, n_past] | None)"""
+        c = self.c
+        M = c.q_tokens if c.q_tokens > 0 else c.mem_tokens
+        B = max(self.batch, 1)
+        nf = c.depth * c.heads * M * c.max_chunk_frames
+        per = nf + c.heads * M * c.cache_cap
+        v = self.maps[:B * per].view(B, per)
+        form = v[:, :c.depth * c.heads * M * F].reshape(B, c.depth, c.heads, M, F).clone()
+        evo = v[:, nf:nf + c.heads * M * n_past].reshape(B, c.heads, M, n_past).clone() if n_past > 0 else None
+        return form, evo
+
     def __del__(self):
         try:
             if self.ctx:
@@ -387,6 +438,8 @@ class TransformerProjector(nn.Module):
         self.memory_update_attention = Attention(self.config)
         self.frame_attn_scores: List[torch.Tensor] = []
         self.compute_frame_scores = True      # API parity default; False skips the column-sum pass
+        self.record_attention_maps = False    # True: every inference forward appends an AttentionMaps to `attention_maps`
+        self.attention_maps: List[AttentionMaps] = []
         self._memory_cache: List[torch.Tensor] = []
         self._cache_mode = "engine"           # "engine": ring views (inference); "autograd": graph tensors (training)
         self._evo_kv = []                     # training path: (K, V) projections of the cached memories
@@ -415,6 +468,7 @@ class TransformerProjector(nn.Module):
                                   "its entries are views into the module's ring buffer")
         self._memory_cache = value
         self._evo_kv = []
+        self.attention_maps = []
         self._cache_mode = "engine"
         if self._engine is not None:
             capi.check(capi.lib().mavlm_reset(self._engine.ctx), "mavlm_reset")
@@ -497,6 +551,7 @@ class TransformerProjector(nn.Module):
         r._memory_cache = []
         r._evo_kv = []
         r.frame_attn_scores = []
+        r.attention_maps = []
         r._fused_ln_never = bool(fused_ln_never)
         return r
 
@@ -549,11 +604,19 @@ class TransformerProjector(nn.Module):
         x = image_features.contiguous()
         scores = torch.empty(F, device=x.device, dtype=x.dtype) if self.compute_frame_scores else None
         lib = capi.lib()
+        record = bool(self.record_attention_maps)
+        if record and torch.cuda.is_current_stream_capturing():
+            raise capi.MavlmError("record_attention_maps: the maps are written by eager steps, not inside a graph capture")
+        eng.set_maps(record)
+        n_past = lib.mavlm_cache_len(eng.ctx)
         rc = lib.mavlm_step(eng.ctx, x.data_ptr(), F, scores.data_ptr() if scores is not None else 0, 0, ops.stream_ptr())
         if rc == capi.E_STATE and torch.cuda.is_current_stream_capturing():
             raise capi.MavlmError("mavlm_step inside a graph capture: the step needs an eager step first (a K/V projection of "
                                   "`project_ahead` still pending in its buffer, or the first fused step of a new workspace)")
         capi.check(rc, "mavlm_step")
+        if record:
+            form, evo = eng.read_maps(F, n_past)
+            self.attention_maps.append(AttentionMaps(form[0], evo[0] if evo is not None else None))
         self._memory_cache.append(eng.mem_ring[lib.mavlm_newest_slot(eng.ctx)])      # :152
         cap = eng.c.cache_cap
         if len(self._memory_cache) > cap:                                            # :153-154
@@ -568,6 +631,9 @@ class TransformerProjector(nn.Module):
         are the HIP kernels (_autograd.py), in the kernel order of the fused inference step - the activations are
         bit-identical to mavlm_step's.  The FIFO holds graph-carrying tensors instead of ring views."""
         from ... import _autograd as ag
+        if self.record_attention_maps:
+            raise capi.MavlmError("record_attention_maps is not supported on the autograd (training) path: attention maps are "
+                                  "recorded by inference forwards only (torch.no_grad() or frozen parameters)")
         if self._cache_mode == "engine" and self._memory_cache:
             raise capi.MavlmError("memory_cache holds ring views of an inference-mode video: reset it "
                                   "(`memory_cache = []`) before running the training path")
@@ -647,6 +713,8 @@ class BatchedProjector:
         self._packed_epoch = -1
         self.compute_frame_scores = True
         self.frame_scores: List[torch.Tensor] = []
+        self.record_attention_maps = False    # True: every step appends an AttentionMaps with a leading video axis
+        self.attention_maps: List[AttentionMaps] = []
         self._n = 0
 
     def engine(self, device, dtype, frames=None) -> _Engine:
@@ -668,6 +736,7 @@ class BatchedProjector:
     def reset(self):
         """`memory_cache = []` for every video of the batch (llava_arch.py:532)."""
         self.frame_scores = []
+        self.attention_maps = []
         self._n = 0
         if self._engine is not None:
             capi.check(capi.lib().mavlm_reset(self._engine.ctx), "mavlm_reset")
@@ -689,8 +758,15 @@ class BatchedProjector:
         eng = self.engine(segs[0].device, segs[0].dtype, F)
         ptrs = (capi.vp * self.batch)(*[t.data_ptr() for t in segs])
         scores = torch.empty((self.batch, F), device=segs[0].device, dtype=segs[0].dtype) if self.compute_frame_scores else None
+        record = bool(self.record_attention_maps)
+        if record and torch.cuda.is_current_stream_capturing():
+            raise capi.MavlmError("record_attention_maps: the maps are written by eager steps, not inside a graph capture")
+        eng.set_maps(record)
+        n_past = capi.lib().mavlm_cache_len(eng.ctx)
         capi.check(capi.lib().mavlm_step_batch(eng.ctx, ptrs, F, scores.data_ptr() if scores is not None else 0, 0,
                                                ops.stream_ptr()), "mavlm_step_batch")
+        if record:
+            self.attention_maps.append(AttentionMaps(*eng.read_maps(F, n_past)))
         self._n += 1
         if scores is not None:
             self.frame_scores.append(scores)
