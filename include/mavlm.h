@@ -209,6 +209,36 @@ int mavlm_fuse_emit_batch(mavlm_ctx* ctx, const void* const* x_pe, const int64_t
                           const void* mem_prompt, int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt,
                           const void* newline, int32_t with_frames, void* out, int64_t rows_per_video, int64_t* rows,
                           void* stream);
+/* Video token layouts: where the reference puts `image_newline` rows into a block of N feature groups of `patches` rows (the
+ * n*M fused memory tokens, or the fine frames; each block is laid out on its own).  Replaces the mm_patch_merge_type /
+ * mm_newline_position branches of llava_arch.py:567-569 (flat), :585-634 (spatial*):
+ *   MAVLM_LAYOUT_ONE    one newline behind the block (:620-629, "one_token" with an *_unpad merge type) - what mavlm_fuse_emit writes
+ *   MAVLM_LAYOUT_NONE   the rows, no newline (:567-569 "flat", :631-632 "no_token", :620-629 "one_token" without unpad)
+ *   MAVLM_LAYOUT_FRAME  one newline after every `patches` rows (add_token_per_frame, :353-357)
+ *   MAVLM_LAYOUT_GRID   one newline after every sqrt(patches) rows (add_token_per_grid, :330-351); patches must be a square */
+#define MAVLM_LAYOUT_ONE 0
+#define MAVLM_LAYOUT_NONE 1
+#define MAVLM_LAYOUT_FRAME 2
+#define MAVLM_LAYOUT_GRID 3
+/* mavlm_fuse_emit with a layout (llava_arch.py:513-524,545-554,567-569,585-634,708-731):
+ *   out = [mem_prompt ; layout(fused memory) ; frame_prompt ; layout(fine frames)]
+ * The same launches as mavlm_fuse_emit with other destination rows - the feature rows are bit-identical in every layout.
+ * `newline` may be null for MAVLM_LAYOUT_NONE.  MAVLM_E_SHAPE: _GRID with a `patches` that is not a square.  *rows =
+ * mavlm_layout_rows(...).  mavlm_fuse_emit(...) = this call with MAVLM_LAYOUT_ONE. */
+int mavlm_fuse_emit_layout(mavlm_ctx* ctx, const void* x_pe, const int64_t* fine_idx, int32_t n_fine, const void* mem_prompt,
+                           int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt, const void* newline,
+                           int32_t with_frames, int32_t layout, void* out, int64_t out_capacity_rows, int64_t* rows,
+                           void* stream);
+/* mavlm_fuse_emit_batch with a layout (same reference lines; one video per forward there, llava_arch.py:436) */
+int mavlm_fuse_emit_layout_batch(mavlm_ctx* ctx, const void* const* x_pe, const int64_t* fine_idx, int32_t n_fine,
+                                 const void* mem_prompt, int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt,
+                                 const void* newline, int32_t with_frames, int32_t layout, void* out, int64_t rows_per_video,
+                                 int64_t* rows, void* stream);
+/* Host only: rows of the token block of a video with n_memories cached memories and n_fine fine frames in a layout - the
+ * sequence length the concat of llava_arch.py:722-731 ends up with after :567-634.  <0: MAVLM_E_ARG (bad config / counts /
+ * layout), MAVLM_E_SHAPE (_GRID: patches is not a square). */
+int64_t mavlm_layout_rows(const mavlm_config* cfg, int32_t n_memories, int32_t n_fine, int32_t n_mem_prompt,
+                          int32_t n_frame_prompt, int32_t with_frames, int32_t layout);
 
 /* --- operator-level entry points (used by the parity tests; same kernels the step uses) --------------- */
 /* C = epi(A[M,K] . W[N,K]^T + bias); epilogue: 0 bias, 1 bias+ReLU, 2 bias+GELU(erf),

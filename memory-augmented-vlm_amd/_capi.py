@@ -12,6 +12,9 @@ MAX_DEPTH = 8
 BF16, F16 = 0, 1
 EPI_BIAS, EPI_RELU, EPI_GELU, EPI_RES_F32, EPI_F32 = 0, 1, 2, 3, 4
 E_ARG, E_SHAPE, E_STATE = -1, -2, -3
+# MAVLM_LAYOUT_*: where image_newline rows go in the video token block, by the names model/llava_arch.py token_layout() returns
+LAYOUT_ONE, LAYOUT_NONE, LAYOUT_FRAME, LAYOUT_GRID = 0, 1, 2, 3
+LAYOUTS = {"one_token": LAYOUT_ONE, "no_token": LAYOUT_NONE, "frame": LAYOUT_FRAME, "grid": LAYOUT_GRID}
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -70,6 +73,11 @@ SIGNATURES = {
                                         C.POINTER(C.c_int64), vp]),
     "mavlm_fuse_emit": (C.c_int, [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, C.c_int64,
                                   C.POINTER(C.c_int64), vp]),
+    "mavlm_fuse_emit_layout_batch": (C.c_int, [vp, C.POINTER(vp), vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64,
+                                               C.POINTER(C.c_int64), vp]),
+    "mavlm_fuse_emit_layout": (C.c_int, [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64,
+                                         C.POINTER(C.c_int64), vp]),
+    "mavlm_layout_rows": (C.c_int64, [C.POINTER(Config), i32, i32, i32, i32, i32, i32]),
     "mavlm_linear": (C.c_int, [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mavlm_attention": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, C.c_float, i32, vp]),
     "mavlm_attention_hd": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, C.c_float, i32, vp]),

@@ -275,11 +275,13 @@ __global__ __launch_bounds__(256) void row_add_kernel(const uint16_t* __restrict
 
 // row_add_kernel for the videos of a row batch in ONE launch (blockIdx.y = video): the fine-frame gather + token-type add of
 // mavlm_fuse_emit_batch (llava_arch.py:620-629), one source pointer per video, the videos' outputs vstride elements apart
+// GAP (an instantiation of its own): output row r lands r / gap rows further down - the rows left free are the newline rows
+// of the `grid` / `frame` token layouts (llava_arch.py:330-357), written by copy_rows_kernel
 struct row_add_srcs { const uint16_t* p[16]; };
-template <typename T>
+template <typename T, bool GAP = false>
 __global__ __launch_bounds__(256) void row_add_batch_kernel(row_add_srcs xs, const int64_t* __restrict__ src,
                                                             const uint16_t* __restrict__ table, uint16_t* __restrict__ out,
-                                                            long long vstride, int T_, int P, int D) {
+                                                            long long vstride, int T_, int P, int D, int gap) {
   const uint16_t* __restrict__ x = xs.p[blockIdx.y];
   out += (size_t)blockIdx.y * vstride;
   const int dv = D >> 3;
@@ -295,22 +297,38 @@ __global__ __launch_bounds__(256) void row_add_batch_kernel(row_add_srcs xs, con
     u16x8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = T::from_f32(T::to_f32(a[e]) + T::to_f32(b[e]));
-    *(u16x8*)(out + rowi * D + 8 * c) = o;
+    *(u16x8*)(out + (GAP ? rowi + rowi / (size_t)gap : rowi) * D + 8 * c) = o;
+  }
+}
+
+// out row r + r / gap = in row r: the contiguous 16-bit rows of a writer without a row map, placed into a gapped token block
+__global__ __launch_bounds__(256) void spread_rows_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
+                                                          size_t rows, int D, int gap) {
+  const int dv = D >> 3;
+  const size_t total = rows * dv;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / dv;
+    const int c = (int)(i - r * dv);
+    *(u16x8*)(out + (r + r / (size_t)gap) * D + 8 * c) = *(const u16x8*)(in + r * D + 8 * c);
   }
 }
 
 // The literal rows of a video's token block (llava_arch.py:541-543,559-566: memory prompt, image_newline, frame prompt,
-// image_newline) - up to four short row runs copied to fixed rows of every video's block in ONE launch.
+// image_newline) - up to four short row runs copied to fixed rows of every video's block in ONE launch.  A run with rep > 0
+// is ONE source row written n times, every rep rows: the newline after every 14 (`grid`, add_token_per_grid :330-351) or 196
+// (`frame`, add_token_per_frame :353-357) rows of a block.
 struct copy_rows_args {
   const uint16_t* src[4];
   int n[4];            // rows of run i (0 = unused)
   long long dst[4];    // first row of run i inside a video's block
+  int rep[4];          // 0: n consecutive source rows to consecutive rows; > 0: source row 0 to rows dst, dst + rep, ...
 };
 __global__ __launch_bounds__(256) void copy_rows_kernel(copy_rows_args a, uint16_t* __restrict__ out, long long vstride, int D) {
   int r = blockIdx.x, i = 0;
   while (i < 3 && r >= a.n[i]) r -= a.n[i++];
-  const u16x8* s = (const u16x8*)(a.src[i] + (size_t)r * D);
-  u16x8* d = (u16x8*)(out + (size_t)blockIdx.y * vstride + (size_t)(a.dst[i] + r) * D);
+  const int rp = a.rep[i];
+  const u16x8* s = (const u16x8*)(a.src[i] + (rp > 0 ? (size_t)0 : (size_t)r * D));
+  u16x8* d = (u16x8*)(out + (size_t)blockIdx.y * vstride + (size_t)(a.dst[i] + (rp > 0 ? (long long)r * rp : (long long)r)) * D);
   for (int c = threadIdx.x; c < (D >> 3); c += 256) d[c] = s[c];
 }
 
@@ -441,9 +459,9 @@ hipError_t mavlm_launch_row_add(const void* x, const int64_t* src, const void* t
 }
 
 hipError_t mavlm_launch_row_add_batch(const void* const* x, const int64_t* src, const void* table_row, void* out,
-                                      long long vstride, int B, int T_, int P, int D, int dtype, hipStream_t s) {
+                                      long long vstride, int B, int T_, int P, int D, int dtype, hipStream_t s, int gap) {
   if (T_ <= 0 || B <= 0) return hipSuccess;
-  if (!x || !table_row || !out || P <= 0 || D <= 0 || (D & 7)) return hipErrorInvalidValue;
+  if (!x || !table_row || !out || P <= 0 || D <= 0 || (D & 7) || gap < 0) return hipErrorInvalidValue;
   const size_t total = (size_t)T_ * P * (D >> 3);
   mavlm_prof_scope prof(MAVLM_K_ROWADD, 0.0, 4.0 * B * T_ * (double)P * D, s);
   size_t blocks = (total + 255) / 256;
@@ -456,18 +474,21 @@ hipError_t mavlm_launch_row_add_batch(const void* const* x, const int64_t* src, 
       xs.p[i] = (const uint16_t*)x[b0 + i];
     }
     uint16_t* o = (uint16_t*)out + (size_t)b0 * vstride;
-    if (dtype == MAVLM_F16)
-      hipLaunchKernelGGL(row_add_batch_kernel<F16>, dim3((unsigned)blocks, (unsigned)nb), dim3(256), 0, s, xs, src,
-                         (const uint16_t*)table_row, o, vstride, T_, P, D);
-    else
-      hipLaunchKernelGGL(row_add_batch_kernel<BF16>, dim3((unsigned)blocks, (unsigned)nb), dim3(256), 0, s, xs, src,
-                         (const uint16_t*)table_row, o, vstride, T_, P, D);
+#define RAB(TT, GG)                                                                                                    \
+  hipLaunchKernelGGL((row_add_batch_kernel<TT, GG>), dim3((unsigned)blocks, (unsigned)nb), dim3(256), 0, s, xs, src, \
+                     (const uint16_t*)table_row, o, vstride, T_, P, D, gap)
+    if (dtype == MAVLM_F16) {
+      if (gap > 0) RAB(F16, true); else RAB(F16, false);
+    } else {
+      if (gap > 0) RAB(BF16, true); else RAB(BF16, false);
+    }
+#undef RAB
   }
   return hipGetLastError();
 }
 
 hipError_t mavlm_launch_copy_rows(const void* const* src, const int* n, const long long* dst, int runs, void* out,
-                                  long long vstride, int B, int D, hipStream_t s) {
+                                  long long vstride, int B, int D, hipStream_t s, const int* rep) {
   if (runs < 0 || runs > 4 || !out || B <= 0 || D <= 0 || (D & 7)) return hipErrorInvalidValue;
   copy_rows_args a = {};
   int total = 0, k = 0;
@@ -475,12 +496,26 @@ hipError_t mavlm_launch_copy_rows(const void* const* src, const int* n, const lo
     if (n[i] <= 0) continue;
     if (!src[i]) return hipErrorInvalidValue;
     a.src[k] = (const uint16_t*)src[i]; a.n[k] = n[i]; a.dst[k] = dst[i];
+    a.rep[k] = rep ? rep[i] : 0;
+    if (a.rep[k] < 0) return hipErrorInvalidValue;
     total += n[i];
     ++k;
   }
   if (!total) return hipSuccess;
   mavlm_prof_scope prof(MAVLM_K_ROWADD, 0.0, 4.0 * total * (double)B * D, s);
   hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)total, (unsigned)B), dim3(256), 0, s, a, (uint16_t*)out, vstride, D);
+  return hipGetLastError();
+}
+
+hipError_t mavlm_launch_spread_rows(const void* in, void* out, long long rows, int D, int gap, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (!in || !out || D <= 0 || (D & 7) || gap <= 0 || (((uintptr_t)in | (uintptr_t)out) & 15)) return hipErrorInvalidValue;
+  mavlm_prof_scope prof(MAVLM_K_ROWADD, 0.0, 4.0 * (double)rows * D, s);
+  const size_t total = (size_t)rows * (D >> 3);
+  size_t blocks = (total + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(spread_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const uint16_t*)in, (uint16_t*)out, (size_t)rows,
+                     D, gap);
   return hipGetLastError();
 }
 

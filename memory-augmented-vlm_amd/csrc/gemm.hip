@@ -320,9 +320,19 @@ size_t mavlm_gemm_split_ws_floats(int M, int N, int K, int epilogue, int ldc) {
   return sp > 1 ? (size_t)sp * M * N : 0;
 }
 
+bool mavlm_gemm_row_map_ok(const mavlm_gemm_args& g) {
+  if (g.epilogue == MAVLM_EPI_LN) return false;
+  if (g.c_rpb > 0) return true;               // (row-batched outputs only ever run on the 256-column-tile kernels)
+  if (g.splitk_ws != nullptr && g_mavlm_gemm_tile == 0 && mavlm_gemm_splits(g.M, g.N, g.K, g.epilogue, g.ldc) > 1) return false;
+  return use_128x256(g) || use_256(g);
+}
+
 hipError_t mavlm_launch_gemm(const mavlm_gemm_args& g, int dtype, hipStream_t s) {
   if (g.planes_out) *g.planes_out = 0;
   if (g.M <= 0) return hipSuccess;
+  // gapped output rows: the kernel choice below is the one of c_gap = 0 (same tiles, same split: same bits); where that is
+  // a kernel without a row map the caller writes to a scratch and places the rows itself (mavlm_launch_spread_rows)
+  if (g.c_gap < 0 || (g.c_gap > 0 && (g.epilogue != MAVLM_EPI_BIAS || !mavlm_gemm_row_map_ok(g)))) return hipErrorInvalidValue;
   if (g.epilogue == MAVLM_EPI_LN) {
     // dense + residual + LayerNorm in one kernel: the non-persistent 256-column-tile kernel only (its row-block exchange
     // needs the N / 256 workgroups of a row block in flight together)

@@ -65,13 +65,13 @@ struct IC1 { static constexpr int value = V; };
     __builtin_amdgcn_sched_barrier(0);                         \
   } while (0)
 
-template <typename T, int EPI>
+template <typename T, int EPI, bool GAP = false>
 __global__ __launch_bounds__(256, 2) void gemm128_kernel(const uint16_t* __restrict__ A, int lda,
                                                          const uint16_t* __restrict__ W, int ldw,
                                                          const float* __restrict__ bias,
                                                          const uint16_t* __restrict__ res, int ldr,
                                                          void* __restrict__ Cout, int ldc, int M, int N, int K,
-                                                         int c_rpb, int c_nb, long long c_bs, mavlm_ln_epilogue ln) {
+                                                         int c_rpb, int c_nb, long long c_bs, mavlm_ln_epilogue ln, int c_gap) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -406,10 +406,13 @@ __global__ __launch_bounds__(256, 2) void gemm128_kernel(const uint16_t* __restr
     if (EPI == MAVLM_EPI_GELU) return gelu_erf_fast4(v);      // packed fp32 math (mavlm_common.h)
     return v;
   };
+  // (row-batched and gapped outputs: see gemm256_kernel / mavlm_gemm_args::c_rpb, c_gap)
   auto crow = [&](int m) -> size_t {
-    if (c_rpb <= 0) return (size_t)m * ldc;
+    if (c_rpb <= 0) return (size_t)(GAP ? m + m / c_gap : m) * ldc;
     const int q = m / c_rpb, r = m - q * c_rpb;
-    return (size_t)(q % c_nb) * (size_t)c_bs + ((size_t)(q / c_nb) * c_rpb + r) * ldc;
+    if (!GAP) return (size_t)(q % c_nb) * (size_t)c_bs + ((size_t)(q / c_nb) * c_rpb + r) * ldc;
+    const int v = (q / c_nb) * c_rpb + r;
+    return (size_t)(q % c_nb) * (size_t)c_bs + (size_t)(v + v / c_gap) * ldc;
   };
   f32x4 bv[4];
 #pragma unroll
@@ -443,9 +446,9 @@ __global__ __launch_bounds__(256, 2) void gemm128_kernel(const uint16_t* __restr
   }
 }
 
-template <typename T, int EPI>
+template <typename T, int EPI, bool GAP = false>
 hipError_t launch128(const mavlm_gemm_args& g, hipStream_t s) {
-  auto kern = gemm128_kernel<T, EPI>;
+  auto kern = gemm128_kernel<T, EPI, GAP>;
   static mavlm_per_device_once once;
   {
     hipError_t e = once.dyn_lds((const void*)kern, GEMM128_LDS);
@@ -454,12 +457,14 @@ hipError_t launch128(const mavlm_gemm_args& g, hipStream_t s) {
   const int ntm = (g.M + BM1 - 1) / BM1, ntn = g.N / BN1;
   hipLaunchKernelGGL(kern, dim3(ntm * ntn), dim3(256), GEMM128_LDS, s, (const uint16_t*)g.A, g.lda, (const uint16_t*)g.W,
                      g.ldw, g.bias, (const uint16_t*)g.res, g.ldr, g.C, g.ldc, g.M, g.N, g.K, g.c_rpb, g.c_nb > 0 ? g.c_nb : 1,
-                     (long long)g.c_bstride, g.ln);
+                     (long long)g.c_bstride, g.ln, g.c_gap);
   return hipGetLastError();
 }
 
 template <typename T>
 hipError_t launch128_epi(const mavlm_gemm_args& g, hipStream_t s) {
+  if (g.c_gap > 0)        // gapped output rows: the bias epilogue only (see gemm256.hip launch256)
+    return g.epilogue == MAVLM_EPI_BIAS ? launch128<T, MAVLM_EPI_BIAS, true>(g, s) : hipErrorInvalidValue;
   switch (g.epilogue) {
     case MAVLM_EPI_BIAS: return launch128<T, MAVLM_EPI_BIAS>(g, s);
     case MAVLM_EPI_RELU: return launch128<T, MAVLM_EPI_RELU>(g, s);

@@ -20,6 +20,7 @@ struct mavlm_ctx {
   bool ftiles_ok = false;          // ... and the carve covers its tile-entry form (attention3.hip FR = 2)
   size_t split_floats = 0;         // floats carved at o_split (attention partials: split-KV / stream-K)
   size_t o_lnx = 0, lnx_bytes = 0; // scratch of the fused dense + residual + LayerNorm GEMM epilogue (0 = not used for this config)
+  size_t o_stage = 0, stage_bytes = 0;   // fused memory rows of a gapped token layout where the fuser's last writer has no row map (fuse_stage_bytes)
   // K/V projections of chunks ahead of their step (mavlm_project_chunk: the next step; mavlm_project_chunk_ahead: the one after it,
   // on another stream): two chunk K/V buffers (o_kv, o_kv2; single videos), a slot per buffer
   struct pre_slot {
@@ -112,6 +113,31 @@ size_t gemm_split_floats(const mavlm_config& c) {
     for (size_t n : need) fl = n > fl ? n : fl;
   }
   return fl;
+}
+
+// The fuser's second GEMM of a launch over `rows` memory rows of a single video, as mavlm_fuse_emit issues it (C / split_ws: only
+// their being set and 16-byte aligned matters to the dispatch)
+mavlm_gemm_args fuser_out_gemm(const mavlm_config& c, int rows, void* C, float* split_ws, size_t split_floats) {
+  mavlm_gemm_args g;
+  g.A = nullptr; g.lda = c.inter; g.W = nullptr; g.ldw = c.inter; g.bias = nullptr; g.res = nullptr; g.ldr = 0;
+  g.C = C; g.ldc = c.hidden; g.M = rows; g.N = c.hidden; g.K = c.inter; g.epilogue = MAVLM_EPI_BIAS;
+  if (split_ws != nullptr && mavlm_gemm_split_ws_floats(rows, c.hidden, c.inter, MAVLM_EPI_BIAS, c.hidden) <= split_floats) g.splitk_ws = split_ws;
+  return g;
+}
+
+// Token layouts with newline rows INSIDE the memory block (MAVLM_LAYOUT_FRAME / _GRID): the fuser's second GEMM scatters its
+// rows itself where it runs on a 256-column-tile kernel (mavlm_gemm_args::c_gap).  The small grids of a single video that
+// take the 128^2 kernel or the split-K reduce - writers of M x N contiguous elements - write here instead and one copy
+// kernel places the rows: the bytes of the largest such launch (0 = every launch of this config maps its rows).
+size_t fuse_stage_bytes(const mavlm_config& c, int fuse_mems, size_t gsplit_floats) {
+  if (nbatch(c) > 1) return 0;                      // (a row batch only ever runs the 256-column-tile kernels)
+  size_t rows_max = 0;
+  for (int run = 1; run <= fuse_mems; ++run) {
+    const int rows = run * c.mem_tokens * c.patches;
+    const mavlm_gemm_args g = fuser_out_gemm(c, rows, (void*)(uintptr_t)256, gsplit_floats ? (float*)(uintptr_t)256 : nullptr, gsplit_floats);
+    if (!mavlm_gemm_row_map_ok(g)) rows_max = (size_t)rows;
+  }
+  return rows_max * (size_t)c.hidden * 2;
 }
 
 void carve(mavlm_ctx* x) {
@@ -230,6 +256,9 @@ void carve(mavlm_ctx* x) {
       }
     if (x->lnx_bytes) { x->o_lnx = o; o += al(x->lnx_bytes); }
   }
+  x->o_stage = 0;
+  x->stage_bytes = fuse_stage_bytes(c, x->fuse_mems, x->gsplit_floats);
+  if (x->stage_bytes) { x->o_stage = o; o += al(x->stage_bytes); }
   x->total = o;
 }
 
@@ -848,19 +877,43 @@ int mavlm_project_chunk_ahead(mavlm_ctx* x, const void* seg, int32_t F, void* st
 }
 
 namespace {
+// newline period of a token layout (mavlm.h MAVLM_LAYOUT_*): 0 = no newline inside a block (_ONE: one behind it, _NONE: none),
+// else one newline row after every `gap` rows of a block.  <0: MAVLM_E_*.
+int layout_gap(const mavlm_config& c, int32_t layout) {
+  switch (layout) {
+    case MAVLM_LAYOUT_ONE:
+    case MAVLM_LAYOUT_NONE: return 0;
+    case MAVLM_LAYOUT_FRAME: return c.patches;
+    case MAVLM_LAYOUT_GRID: {
+      int g = (int)(sqrt((double)c.patches) + 0.5);
+      return g > 0 && g * g == c.patches ? g : MAVLM_E_SHAPE;     // (add_token_per_grid views a frame as a square grid, :336-338)
+    }
+  }
+  return MAVLM_E_ARG;
+}
+// rows a block of `rows` feature rows takes in a layout
+inline int64_t block_rows(int64_t rows, int32_t layout, int gap) {
+  return rows + (gap > 0 ? rows / gap : (layout == MAVLM_LAYOUT_ONE ? 1 : 0));
+}
+
 int fuse_emit_impl(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_idx, int32_t n_fine, const void* mem_prompt,
                    int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt, const void* newline,
-                   int32_t with_frames, void* out, int64_t cap_rows, int64_t* rows, hipStream_t s) {
+                   int32_t with_frames, int32_t layout, void* out, int64_t cap_rows, int64_t* rows, hipStream_t s) {
   if (!x->w.w_f1 || !x->w.b_f1 || !x->w.w_f2 || !x->w.b_f2_type0 || (with_frames && !x->w.type1)) return MAVLM_E_STATE;
   if (n_mem_prompt < 0 || n_frame_prompt < 0 || n_fine < 0 || (n_mem_prompt && !mem_prompt) ||
       (with_frames && ((n_frame_prompt && !frame_prompt) || (n_fine && (!x_pe || !fine_idx)))))
     return MAVLM_E_ARG;
   const mavlm_config& c = x->cfg;
+  const int gap = layout_gap(c, layout);
+  if (gap < 0) return gap;
+  if (layout != MAVLM_LAYOUT_NONE && !newline) return MAVLM_E_ARG;
   const int B = nbatch(c), R1 = c.mem_tokens * c.patches, R = R1 * B, D = c.hidden, I = c.inter, dt = c.dtype, cap = c.cache_cap;
   const int n = x->steps < cap ? x->steps : cap;
   if (n == 0) return MAVLM_E_STATE;
-  int64_t need = (int64_t)n_mem_prompt + (int64_t)n * R1 + 1;
-  if (with_frames) need += (int64_t)n_frame_prompt + (int64_t)n_fine * c.patches + 1;
+  // block rows: the memory block and the fine-frame block are laid out SEPARATELY (llava_arch.py:585-634 runs per feature)
+  const int64_t r_mem = n_mem_prompt, mem_rows = block_rows((int64_t)n * R1, layout, gap);
+  const int64_t r_fp = r_mem + mem_rows, r_fine = r_fp + n_frame_prompt, fine_rows = block_rows((int64_t)n_fine * c.patches, layout, gap);
+  const int64_t need = with_frames ? r_fine + fine_rows : r_fp;
   if (cap_rows < need) return MAVLM_E_ARG;
   if (with_frames && n_fine)
     for (int b = 0; b < B; ++b)
@@ -868,18 +921,17 @@ int fuse_emit_impl(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_id
   const size_t rowb = (size_t)D * 2;
   // (video b's token block starts b * cap_rows rows into `out`)
   char* o = (char*)out;
-  int64_t row = 0;
   {
-    // the literal rows (memory prompt, newline, frame prompt, newline) of all B blocks: one launch, rows known up front
-    const int64_t r_nl1 = (int64_t)n_mem_prompt + (int64_t)n * R1, r_fp = r_nl1 + 1;
-    const int64_t r_nl2 = r_fp + n_frame_prompt + (int64_t)n_fine * c.patches;
+    // the literal rows (memory prompt, newlines of the memory block, frame prompt, newlines of the fine block) of all B blocks:
+    // one launch, rows known up front.  gap > 0: a newline behind every `gap` rows, i.e. every gap + 1 output rows.
+    const int nl_mem = (int)(mem_rows - (int64_t)n * R1), nl_fine = (int)(fine_rows - (int64_t)n_fine * c.patches);
     const void* src[4] = {mem_prompt, newline, frame_prompt, newline};
-    const int cnt[4] = {n_mem_prompt, 1, with_frames ? n_frame_prompt : 0, with_frames ? 1 : 0};
-    const long long dst[4] = {0, r_nl1, r_fp, r_nl2};
+    const int cnt[4] = {n_mem_prompt, nl_mem, with_frames ? n_frame_prompt : 0, with_frames ? nl_fine : 0};
+    const long long dst[4] = {0, r_mem + (gap > 0 ? gap : (int64_t)n * R1), r_fp, r_fine + (gap > 0 ? gap : (int64_t)n_fine * c.patches)};
+    const int rep[4] = {0, gap > 0 ? gap + 1 : 0, 0, gap > 0 ? gap + 1 : 0};
     if ((((uintptr_t)mem_prompt | (uintptr_t)newline | (uintptr_t)frame_prompt | (uintptr_t)out) & 15)) return MAVLM_E_ARG;
-    MAVLM_TRY(mavlm_launch_copy_rows(src, cnt, dst, 4, out, (long long)cap_rows * D, B, D, s));
+    MAVLM_TRY(mavlm_launch_copy_rows(src, cnt, dst, 4, out, (long long)cap_rows * D, B, D, s, rep));
   }
-  row += n_mem_prompt;
   const int oldest = x->steps <= cap ? 0 : x->steps % cap;
   // torch.cat(memory_cache) order = oldest first (llava_arch.py:545) = ring slots oldest..cap-1, then 0..oldest-1: at most
   // two contiguous slot ranges, each fused in batches of up to fuse_mems memories per GEMM pair (llava_arch.py:546).  A
@@ -891,50 +943,80 @@ int fuse_emit_impl(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_id
     const int rows_ = run * R;
     const char* mem = (const char*)x->b.mem_ring + (size_t)slot * R * rowb;
     MAVLM_TRY(gemm_x(x, s, mem, D, x->w.w_f1, D, x->w.b_f1, ws(x, x->o_h), I, rows_, I, D, MAVLM_EPI_GELU));
-    if (B == 1) {
-      MAVLM_TRY(gemm_x(x, s, ws(x, x->o_h), I, x->w.w_f2, I, x->w.b_f2_type0, o + (size_t)row * rowb, D, rows_, D, I,
-                       MAVLM_EPI_BIAS));
-    } else {
-      mavlm_gemm_args g;
-      g.A = ws(x, x->o_h); g.lda = I; g.W = x->w.w_f2; g.ldw = I; g.bias = x->w.b_f2_type0; g.res = nullptr; g.ldr = 0;
-      g.C = o + (size_t)row * rowb; g.ldc = D; g.M = rows_; g.N = D; g.K = I; g.epilogue = MAVLM_EPI_BIAS;
+    // first row of this launch inside a video's block (done * R1 is a multiple of the gap: whole frames)
+    const int64_t v0 = (int64_t)done * R1;
+    char* dstp = o + (size_t)(r_mem + v0 + (gap > 0 ? v0 / gap : 0)) * rowb;
+    mavlm_gemm_args g = fuser_out_gemm(c, rows_, dstp, x->gsplit_floats ? (float*)ws(x, x->o_gsplit) : nullptr, x->gsplit_floats);
+    g.A = ws(x, x->o_h); g.W = x->w.w_f2; g.bias = x->w.b_f2_type0;
+    if (B > 1) {
+      g.splitk_ws = nullptr;
       g.c_rpb = R1; g.c_nb = B; g.c_bstride = (long long)cap_rows * D;
+    }
+    if (gap > 0 && !mavlm_gemm_row_map_ok(g)) {
+      // the writer this shape takes has no row map (128^2 kernel / split-K reduce; single videos on small grids): the same
+      // launch into the scratch, then one copy places the rows
+      if ((size_t)rows_ * rowb > x->stage_bytes) return MAVLM_E_STATE;      // (a tuning hook changed the dispatch after mavlm_create)
+      g.C = ws(x, x->o_stage);
+      MAVLM_TRY(mavlm_launch_gemm(g, dt, s));
+      MAVLM_TRY(mavlm_launch_spread_rows(g.C, dstp, rows_, D, gap, s));
+    } else {
+      g.c_gap = gap;
       MAVLM_TRY(mavlm_launch_gemm(g, dt, s));
     }
-    row += (int64_t)run * R1;
     done += run;
   }
-  row += 1;
-  if (with_frames) {
-    row += n_frame_prompt;
-    if (n_fine)
-      MAVLM_TRY(mavlm_launch_row_add_batch(x_pe, fine_idx, x->w.type1, o + (size_t)row * rowb, (long long)cap_rows * D, B, n_fine,
-                                           c.patches, D, dt, s));
-    row += (int64_t)n_fine * c.patches;
-    row += 1;
-  }
-  *rows = row;
+  if (with_frames && n_fine)
+    MAVLM_TRY(mavlm_launch_row_add_batch(x_pe, fine_idx, x->w.type1, o + (size_t)r_fine * rowb, (long long)cap_rows * D, B, n_fine,
+                                         c.patches, D, dt, s, gap));
+  *rows = need;
   return 0;
 }
 }  // namespace
 
-int mavlm_fuse_emit(mavlm_ctx* x, const void* x_pe, const int64_t* fine_idx, int32_t n_fine, const void* mem_prompt,
-                    int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt, const void* newline,
-                    int32_t with_frames, void* out, int64_t cap_rows, int64_t* rows, void* stream) {
-  if (!x || !out || !newline || !rows) return MAVLM_E_ARG;
+int mavlm_fuse_emit_layout(mavlm_ctx* x, const void* x_pe, const int64_t* fine_idx, int32_t n_fine, const void* mem_prompt,
+                           int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt, const void* newline,
+                           int32_t with_frames, int32_t layout, void* out, int64_t cap_rows, int64_t* rows, void* stream) {
+  if (!x || !out || !rows) return MAVLM_E_ARG;
   if (!x->has_w || !x->has_b) return MAVLM_E_STATE;
   if (nbatch(x->cfg) != 1) return MAVLM_E_STATE;
   return fuse_emit_impl(x, x_pe ? &x_pe : nullptr, fine_idx, n_fine, mem_prompt, n_mem_prompt, frame_prompt, n_frame_prompt, newline,
-                        with_frames, out, cap_rows, rows, (hipStream_t)stream);
+                        with_frames, layout, out, cap_rows, rows, (hipStream_t)stream);
+}
+
+int mavlm_fuse_emit_layout_batch(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_idx, int32_t n_fine,
+                                 const void* mem_prompt, int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt,
+                                 const void* newline, int32_t with_frames, int32_t layout, void* out, int64_t rows_per_video,
+                                 int64_t* rows, void* stream) {
+  if (!x || !out || !rows) return MAVLM_E_ARG;
+  if (!x->has_w || !x->has_b) return MAVLM_E_STATE;
+  return fuse_emit_impl(x, x_pe, fine_idx, n_fine, mem_prompt, n_mem_prompt, frame_prompt, n_frame_prompt, newline, with_frames,
+                        layout, out, rows_per_video, rows, (hipStream_t)stream);
+}
+
+int mavlm_fuse_emit(mavlm_ctx* x, const void* x_pe, const int64_t* fine_idx, int32_t n_fine, const void* mem_prompt,
+                    int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt, const void* newline,
+                    int32_t with_frames, void* out, int64_t cap_rows, int64_t* rows, void* stream) {
+  if (!newline) return MAVLM_E_ARG;
+  return mavlm_fuse_emit_layout(x, x_pe, fine_idx, n_fine, mem_prompt, n_mem_prompt, frame_prompt, n_frame_prompt, newline, with_frames,
+                                MAVLM_LAYOUT_ONE, out, cap_rows, rows, stream);
 }
 
 int mavlm_fuse_emit_batch(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_idx, int32_t n_fine, const void* mem_prompt,
                           int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt, const void* newline,
                           int32_t with_frames, void* out, int64_t rows_per_video, int64_t* rows, void* stream) {
-  if (!x || !out || !newline || !rows) return MAVLM_E_ARG;
-  if (!x->has_w || !x->has_b) return MAVLM_E_STATE;
-  return fuse_emit_impl(x, x_pe, fine_idx, n_fine, mem_prompt, n_mem_prompt, frame_prompt, n_frame_prompt, newline, with_frames,
-                        out, rows_per_video, rows, (hipStream_t)stream);
+  if (!newline) return MAVLM_E_ARG;
+  return mavlm_fuse_emit_layout_batch(x, x_pe, fine_idx, n_fine, mem_prompt, n_mem_prompt, frame_prompt, n_frame_prompt, newline,
+                                      with_frames, MAVLM_LAYOUT_ONE, out, rows_per_video, rows, stream);
+}
+
+int64_t mavlm_layout_rows(const mavlm_config* cfg, int32_t n_memories, int32_t n_fine, int32_t n_mem_prompt, int32_t n_frame_prompt,
+                          int32_t with_frames, int32_t layout) {
+  if (!cfg_ok(cfg) || n_memories < 0 || n_fine < 0 || n_mem_prompt < 0 || n_frame_prompt < 0) return MAVLM_E_ARG;
+  const int gap = layout_gap(*cfg, layout);
+  if (gap < 0) return gap;
+  int64_t r = n_mem_prompt + block_rows((int64_t)n_memories * cfg->mem_tokens * cfg->patches, layout, gap);
+  if (with_frames) r += n_frame_prompt + block_rows((int64_t)n_fine * cfg->patches, layout, gap);
+  return r;
 }
 
 int mavlm_linear(const void* A, int32_t lda, const void* W, int32_t ldw, const float* bias, const void* res, int32_t ldr,

@@ -36,6 +36,12 @@ struct mavlm_gemm_args {
   // (mavlm_config::batch) are written to per-video buffers: the evolution K/V ring, the fused-token blocks.
   int c_rpb = 0, c_nb = 1;
   long long c_bstride = 0;
+  // Gapped output rows (256-column-tile kernels, bias epilogue; 0 = none): row v of the [M, ldc] output - of a batch element's
+  // own output when c_rpb > 0 - lands v / c_gap rows further down, i.e. one row is left free after every c_gap rows: the
+  // image_newline rows of the `grid` / `frame` video token layouts (llava_arch.py:330-357), which mavlm_launch_copy_rows
+  // writes.  Same tiles and same arithmetic as c_gap = 0: only the destination differs.  A launch that mavlm_launch_gemm
+  // would run on a kernel without a row map (mavlm_gemm_row_map_ok() false) is refused (hipErrorInvalidValue).
+  int c_gap = 0;
   mavlm_ln_epilogue ln;          // EPI_LN only
 };
 // wide: 1 = rows of up to 4096 columns (test mode), 0 = up to 1024, -1 = the process-wide hook g_mavlm_gemm_ln_wide
@@ -43,6 +49,10 @@ bool mavlm_gemm_ln_supported(int M, int N, int K, int wide = -1);
 extern int g_mavlm_gemm_ln_wide;
 size_t mavlm_gemm_ln_ws_bytes(int M, int N);
 hipError_t mavlm_launch_gemm(const mavlm_gemm_args& g, int dtype, hipStream_t s);
+// does mavlm_launch_gemm run this launch (c_gap aside) on a kernel that maps its output rows - the 256-column-tile kernels -
+// rather than on the 128^2 kernel or through the split-K reduce, which write M x N contiguous elements?  Pure function of
+// the arguments and the tuning hooks, like the dispatch itself.
+bool mavlm_gemm_row_map_ok(const mavlm_gemm_args& g);
 // split-K plan for GEMMs with few output tiles and a long contraction (small M, K >= 2048): 1 = none.  Pure function of
 // the shape: the fused step and the stand-alone operator take the same path.
 int mavlm_gemm_splits(int M, int N, int K, int epilogue, int ldc);
@@ -237,13 +247,19 @@ hipError_t mavlm_launch_row_add(const void* x, const int64_t* src, const void* t
 
 // row_add for B videos in one launch: out[b*vstride + (t*P + p)*D ..] = x[b][src[t], p, :] + table_row[:]  (x = HOST array of B
 // device pointers; vstride in elements)
+// gap > 0: output row r of a video lands r / gap rows further down (the newline rows of a token layout, see c_gap)
 hipError_t mavlm_launch_row_add_batch(const void* const* x, const int64_t* src, const void* table_row, void* out,
-                                      long long vstride, int B, int T, int P, int D, int dtype, hipStream_t s);
+                                      long long vstride, int B, int T, int P, int D, int dtype, hipStream_t s, int gap = 0);
 
 // `runs` (<= 4) literal row runs: out[b*vstride + (dst[i]+r)*D ..] = src[i][r*D ..] for r < n[i], every video b < B
 // (vstride in elements); one launch for the prompt / newline rows of mavlm_fuse_emit
+// rep (null = all 0): run i with rep[i] > 0 is ONE source row written n[i] times, every rep[i] rows from dst[i] on (the newline
+// rows of the `grid` / `frame` layouts: period gap + 1)
 hipError_t mavlm_launch_copy_rows(const void* const* src, const int* n, const long long* dst, int runs, void* out,
-                                  long long vstride, int B, int D, hipStream_t s);
+                                  long long vstride, int B, int D, hipStream_t s, const int* rep = nullptr);
+// out[(r + r / gap) * D ..] = in[r * D ..] for r < rows (16-bit rows of D elements, D % 8 == 0; gap > 0): places the contiguous
+// rows of a writer without a row map (mavlm_gemm_row_map_ok() false) into a gapped token block
+hipError_t mavlm_launch_spread_rows(const void* in, void* out, long long rows, int D, int gap, hipStream_t s);
 
 // out[f, oy*os+ox, :] = bilinear(x[f, side x side, :]) (+ table[idx[f], :] when table != null); os = ceil(side/stride)
 hipError_t mavlm_launch_pool_bilinear(const void* x, void* out, const void* table, const int64_t* idx, int F, int side,

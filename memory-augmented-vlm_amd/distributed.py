@@ -176,7 +176,9 @@ class RowShardedMemory:
         """The Memory-Fuser MLP over the FIFO (llava_arch.py:545-554: `memory_fuser(cat(cache))` + token-type row 0), row
         sharded as the steps are: rank g fuses its memory tokens of every cached memory ([n, M/W, P, D] rows: the MLP is
         row-independent, two HIP GEMMs with the GELU in the first epilogue), ONE all-gather ([W, n, M/W, P, D]) completes
-        the block on every rank.  Returns [n*M, P, D], oldest memory first - the rows the single-GPU path feeds the LLM."""
+        the block on every rank.  Returns [n*M, P, D], oldest memory first - the rows the single-GPU path feeds the LLM.
+        These are memory rows, not a token block: the video token layout (`llava_arch.token_layout`, newline rows) is applied
+        by whoever builds the block from them, so there is nothing layout-specific here."""
         from . import _capi as capi
         from . import _ops as ops
         self.wait()

@@ -8,9 +8,10 @@ Mirrors the memory-specific parts of the reference's llava/model/llava_arch.py s
                             (llava_arch.py:117-150) - same state-dict keys, so checkpoints load unchanged.
   LlavaMetaForCausalLM      `prepare_inputs_labels_for_multimodal` (8 in / 6 out, llava_arch.py:388-878) for the
                             video path, `get_2dPool`, `encode_images`, `get_synced_dropout_decision`.
-  video_memory_tokens       the per-video driver (llava_arch.py:502-557,613-629,705-731) as HIP launches only:
+  video_memory_tokens       the per-video driver (llava_arch.py:502-557,567-634,705-731) as HIP launches only:
                             PE add -> chunk loop (mavlm_step) -> fuser MLP + type add + prompts/newlines concat
-                            (mavlm_fuse_emit) written straight into one token block.
+                            (mavlm_fuse_emit_layout) written straight into one token block, in the layout
+                            `token_layout(config)` reads from mm_patch_merge_type / mm_newline_position.
 
 Non-video inputs behave as in the reference (round 3): a plain image batch takes the reference's tensor branch (:703,
 backbone ops, restated in torch); a list without a video fails as the reference's memory loop does (IndexError); images
@@ -125,15 +126,85 @@ def _device_indices(idx_cpu: torch.Tensor, device) -> torch.Tensor:
     return t
 
 
+LAYOUTS = ("one_token", "no_token", "frame", "grid")
+
+
+def token_layout(config) -> str:
+    """Layout of the video token block for a model config: where the reference puts `image_newline` rows into the memory
+    block and into the fine-frame block (llava_arch.py:562-634) -
+      "one_token"  one newline behind each block (spatial*_unpad + one_token, :620-629),
+      "no_token"   none (flat, :567-569; spatial* + no_token, :631-632; spatial* without unpad + one_token, :623),
+      "frame"      one after every 196 rows (add_token_per_frame, :353-357),
+      "grid"       one after every 14 rows (add_token_per_grid, :330-351).
+    The one place that reads mm_patch_merge_type, mm_newline_position and add_faster_video; raises what the reference raises
+    (ValueError, :634 / :701).  `grid` with add_faster_video reads tensors the memory branch never creates: NotImplementedError."""
+    merge = getattr(config, "mm_patch_merge_type", "flat")                                  # :562
+    pos = getattr(config, "mm_newline_position", "one_token")                              # :564
+    if merge == "flat":
+        return "no_token"                                                                  # :567-569 (the position is ignored)
+    if not merge.startswith("spatial"):
+        raise ValueError(f"Unexpected mm_patch_merge_type: {merge}")                       # :701
+    if pos == "grid":
+        if getattr(config, "add_faster_video", False):
+            raise NotImplementedError("memory path: mm_newline_position='grid' with add_faster_video (llava_arch.py:590-601 "
+                                      "reads faster-video features the memory branch never creates)")
+        return "grid"
+    if pos == "frame":
+        return "frame"
+    if pos == "one_token":
+        return "one_token" if "unpad" in merge else "no_token"                             # :623
+    if pos == "no_token":
+        return "no_token"
+    raise ValueError(f"Unexpected mm_newline_position: {pos}")                             # :634
+
+
+def layout_period(layout: str, patches: int = 196) -> int:
+    """Newline period of a layout inside a block: 0 = none inside it ("one_token": one behind it; "no_token": none at all),
+    else one newline row after every `period` rows ("frame": a frame's patches; "grid": one row of its square patch grid)."""
+    if layout not in LAYOUTS:
+        raise ValueError(f"unknown token layout {layout!r}: one of {LAYOUTS}")
+    if layout == "frame":
+        return patches
+    if layout == "grid":
+        g = math.isqrt(patches)
+        if g * g != patches:
+            raise ValueError(f"token layout 'grid' needs a square patch grid, not {patches} patches per frame")
+        return g
+    return 0
+
+
+def layout_block_rows(rows: int, layout: str, patches: int = 196) -> int:
+    """Rows a block of `rows` feature rows (whole frames) takes in a layout."""
+    g = layout_period(layout, patches)
+    return rows + (rows // g if g else (1 if layout == "one_token" else 0))
+
+
+def _require_newline(image_newline, layout):
+    """The reference creates `image_newline` only for an *_unpad merge type (llava_arch.py:114) and fails with AttributeError
+    where a layout reads it on a model without one; a layout that inserts nothing needs none."""
+    if layout != "no_token" and image_newline is None:
+        raise AttributeError(f"token layout {layout!r} inserts `image_newline` rows, but the model has no image_newline (the "
+                             "reference creates it only when mm_patch_merge_type contains 'unpad', llava_arch.py:114)")
+
+
+def _newline_ptr(image_newline, layout, device, dtype):
+    """(tensor kept alive, device pointer) of the newline row a layout inserts; (None, None) for a layout that inserts nothing"""
+    _require_newline(image_newline, layout)
+    if layout == "no_token":
+        return None, None
+    nl = image_newline.to(device=device, dtype=dtype).contiguous()
+    return nl, nl.data_ptr()
+
+
 def video_token_rows(num_frames: int, mem_tokens: int, patches: int = 196, with_frames: bool = True, chunk: int = 32,
                      fine_frames: int = 32, cache_cap: int = 10, n_mem_prompt: int = len(MEMORY_PROMPT_IDS),
-                     n_frame_prompt: int = len(FRAME_PROMPT_IDS)) -> int:
+                     n_frame_prompt: int = len(FRAME_PROMPT_IDS), layout: str = "one_token") -> int:
     """Rows of the token block video_memory_tokens() produces for a T-frame video (host arithmetic only), so a caller
-    can allocate the final sequence once and have the block emitted in place."""
+    can allocate the final sequence once and have the block emitted in place.  `layout`: see token_layout()."""
     n = min(-(-num_frames // chunk), cache_cap)
-    rows = n_mem_prompt + n * mem_tokens * patches + 1
+    rows = n_mem_prompt + layout_block_rows(n * mem_tokens * patches, layout, patches)
     if with_frames:
-        rows += n_frame_prompt + min(fine_frames, num_frames) * patches + 1
+        rows += n_frame_prompt + layout_block_rows(min(fine_frames, num_frames) * patches, layout, patches)
     return rows
 
 
@@ -141,14 +212,18 @@ PROJECT_AHEAD = None      # None: automatic (TransformerProjector.ahead_ok), Tru
 
 
 def video_memory_tokens(model, image: torch.Tensor, frame_idx_cpu: torch.Tensor, memory_prompt_embeds: torch.Tensor,
-                        frame_prompt_embeds: torch.Tensor, image_newline: torch.Tensor, with_frames: bool = True,
-                        chunk: int = 32, fine_frames: int = 32, out: Optional[torch.Tensor] = None):
+                        frame_prompt_embeds: torch.Tensor, image_newline: Optional[torch.Tensor], with_frames: bool = True,
+                        chunk: int = 32, fine_frames: int = 32, out: Optional[torch.Tensor] = None, layout: str = "one_token"):
     """Per-video memory path.  `model` owns the four memory sub-modules; `image` = pooled frame tokens [T,196,D]
     on the GPU; `frame_idx_cpu` = original frame indices [T] (host).  Returns (tokens [rows,D], info dict).
 
     tokens = [mem_prompt ; fused memory (oldest first) ; newline ; frame_prompt ; fine frames ; newline]
     (llava_arch.py:620-629,729-731); with_frames=False reproduces the frame-dropout branch (:720-725).
+    `layout` (token_layout(config): "one_token" above, "no_token", "frame", "grid") moves the newlines: none, or one after every
+    196 / 14 rows of the memory block and of the fine-frame block (:567-634); the other rows are the same bits in every layout.
+    `image_newline` may be None for "no_token".
     `out`: optional contiguous [rows, D] destination (e.g. a slice of the final inputs_embeds buffer)."""
+    layout_period(layout, image.shape[1])                                                 # (ValueError for an unknown layout)
     if not image.is_cuda:
         raise capi.MavlmError("video_memory_tokens: frame tokens are not on a GPU (no CPU fallback)")
     pe: TemporalPositionalEncoding = model.positional_encoding
@@ -173,41 +248,45 @@ def video_memory_tokens(model, image: torch.Tensor, frame_idx_cpu: torch.Tensor,
         # (nothing to differentiate there) and only the tail below records a graph - on CLONES of the ring views, which
         # the next video would overwrite before backward.
         return _video_memory_tokens_autograd(model, rm, x, fine_cpu, memory_prompt_embeds, frame_prompt_embeds,
-                                             image_newline, with_frames, out)
+                                             image_newline, with_frames, out, layout)
     eng = rm.engine(image.device, image.dtype)
     n = len(rm.memory_cache)
     R = rm.num_memory_tokens * P
     n_fine = fine_cpu.numel()
-    rows = memory_prompt_embeds.shape[0] + n * R + 1
+    mem_rows = layout_block_rows(n * R, layout, P)
+    rows = memory_prompt_embeds.shape[0] + mem_rows
     if with_frames:
-        rows += frame_prompt_embeds.shape[0] + n_fine * P + 1
+        rows += frame_prompt_embeds.shape[0] + layout_block_rows(n_fine * P, layout, P)
     if out is None:
         out = torch.empty((rows, D), device=image.device, dtype=image.dtype)
     elif tuple(out.shape) != (rows, D) or out.dtype != image.dtype or not out.is_contiguous() or not out.is_cuda:
         raise capi.MavlmError(f"video_memory_tokens: `out` must be a contiguous [{rows},{D}] {image.dtype} GPU tensor")
     mp = memory_prompt_embeds.to(image.dtype).contiguous()
     fp = frame_prompt_embeds.to(image.dtype).contiguous()
-    nl = image_newline.to(device=image.device, dtype=image.dtype).contiguous()
+    nl, nl_ptr = _newline_ptr(image_newline, layout, image.device, image.dtype)
     import ctypes
     written = ctypes.c_int64(0)
-    capi.check(capi.lib().mavlm_fuse_emit(eng.ctx, x.data_ptr(), _device_indices(fine_cpu, image.device).data_ptr(), n_fine,
-                                          mp.data_ptr(), mp.shape[0], fp.data_ptr(), fp.shape[0], nl.data_ptr(),
-                                          1 if with_frames else 0, out.data_ptr(), rows, ctypes.byref(written),
-                                          ops.stream_ptr()), "mavlm_fuse_emit")
+    capi.check(capi.lib().mavlm_fuse_emit_layout(eng.ctx, x.data_ptr(), _device_indices(fine_cpu, image.device).data_ptr(), n_fine,
+                                                 mp.data_ptr(), mp.shape[0], fp.data_ptr(), fp.shape[0], nl_ptr,
+                                                 1 if with_frames else 0, capi.LAYOUTS[layout], out.data_ptr(), rows,
+                                                 ctypes.byref(written), ops.stream_ptr()), "mavlm_fuse_emit_layout")
     assert written.value == rows
-    info = {"num_memories": n, "pe_frames": x, "fine_idx": fine_cpu, "memory_rows": (mp.shape[0], mp.shape[0] + n * R)}
+    # memory_rows: the memory block with the newlines INSIDE it ("frame" / "grid"), without the one behind it ("one_token")
+    info = {"num_memories": n, "pe_frames": x, "fine_idx": fine_cpu,
+            "memory_rows": (mp.shape[0], mp.shape[0] + (mem_rows if layout_period(layout, P) else n * R))}
     return out, info
 
 
 @torch.no_grad()
 def video_memory_tokens_batched(model, bp: BatchedProjector, images, frame_idx_cpu: torch.Tensor,
                                 memory_prompt_embeds: torch.Tensor, frame_prompt_embeds: torch.Tensor,
-                                image_newline: torch.Tensor, with_frames: bool = True, chunk: int = 32,
-                                fine_frames: int = 32, out: Optional[torch.Tensor] = None):
+                                image_newline: Optional[torch.Tensor], with_frames: bool = True, chunk: int = 32,
+                                fine_frames: int = 32, out: Optional[torch.Tensor] = None, layout: str = "one_token"):
     """`video_memory_tokens` for B videos of the SAME length stepped together (row batch, `BatchedProjector`): every
     weight-shared GEMM / LayerNorm of the path runs once over the stacked memory rows of all videos.  `images`: B tensors
     [T,196,D]; `frame_idx_cpu`: the original frame indices (shared: same length, same sampling).  Returns
-    (tokens [B, rows, D] - video b's block is tokens[b] -, info).  Inference only."""
+    (tokens [B, rows, D] - video b's block is tokens[b] -, info).  Inference only.  `layout`: as video_memory_tokens."""
+    layout_period(layout, images[0].shape[1])
     B = bp.batch
     if len(images) != B:
         raise capi.MavlmError(f"video_memory_tokens_batched: {B} videos expected")
@@ -230,25 +309,27 @@ def video_memory_tokens_batched(model, bp: BatchedProjector, images, frame_idx_c
     n = min(len(bounds) - 1, eng.c.cache_cap)
     R = rm.num_memory_tokens * P
     n_fine = fine_cpu.numel()
-    rows = memory_prompt_embeds.shape[0] + n * R + 1
+    mem_rows = layout_block_rows(n * R, layout, P)
+    rows = memory_prompt_embeds.shape[0] + mem_rows
     if with_frames:
-        rows += frame_prompt_embeds.shape[0] + n_fine * P + 1
+        rows += frame_prompt_embeds.shape[0] + layout_block_rows(n_fine * P, layout, P)
     if out is None:
         out = torch.empty((B, rows, D), device=dev, dtype=dt)
     elif tuple(out.shape) != (B, rows, D) or out.dtype != dt or not out.is_contiguous() or not out.is_cuda:
         raise capi.MavlmError(f"video_memory_tokens_batched: `out` must be a contiguous [{B},{rows},{D}] {dt} GPU tensor")
     mp = memory_prompt_embeds.to(dt).contiguous()
     fp = frame_prompt_embeds.to(dt).contiguous()
-    nl = image_newline.to(device=dev, dtype=dt).contiguous()
+    nl, nl_ptr = _newline_ptr(image_newline, layout, dev, dt)
     import ctypes
     written = ctypes.c_int64(0)
     xptrs = (capi.vp * B)(*[x.data_ptr() for x in xs])
-    capi.check(capi.lib().mavlm_fuse_emit_batch(eng.ctx, xptrs, _device_indices(fine_cpu, dev).data_ptr(), n_fine,
-                                                mp.data_ptr(), mp.shape[0], fp.data_ptr(), fp.shape[0], nl.data_ptr(),
-                                                1 if with_frames else 0, out.data_ptr(), rows, ctypes.byref(written),
-                                                ops.stream_ptr()), "mavlm_fuse_emit_batch")
+    capi.check(capi.lib().mavlm_fuse_emit_layout_batch(eng.ctx, xptrs, _device_indices(fine_cpu, dev).data_ptr(), n_fine,
+                                                       mp.data_ptr(), mp.shape[0], fp.data_ptr(), fp.shape[0], nl_ptr,
+                                                       1 if with_frames else 0, capi.LAYOUTS[layout], out.data_ptr(), rows,
+                                                       ctypes.byref(written), ops.stream_ptr()), "mavlm_fuse_emit_layout_batch")
     assert written.value == rows
-    info = {"num_memories": n, "pe_frames": xs, "fine_idx": fine_cpu, "memory_rows": (mp.shape[0], mp.shape[0] + n * R),
+    info = {"num_memories": n, "pe_frames": xs, "fine_idx": fine_cpu,
+            "memory_rows": (mp.shape[0], mp.shape[0] + (mem_rows if layout_period(layout, P) else n * R)),
             "frame_scores": bp.frame_scores}
     return out, info
 
@@ -269,10 +350,20 @@ def path_wants_grad(model, *tensors) -> bool:
                                         or _tail_wants_grad(model, *tensors))
 
 
+def _lay_out_block(block, nl, layout, patches):
+    """A [rows, D] block in a token layout, as torch ops: the feature rows are copied (the same bits in every layout), the
+    newline rows are an expand of `nl` [1, D], whose backward sums the gradient of every inserted row (llava_arch.py:338,355)."""
+    g = layout_period(layout, patches)
+    if g:
+        b = block.reshape(-1, g, block.shape[-1])
+        return torch.cat((b, nl.expand(b.shape[0], 1, b.shape[-1])), dim=1).reshape(-1, block.shape[-1])
+    return torch.cat((block, nl), dim=0) if layout == "one_token" else block
+
+
 def _video_memory_tokens_autograd(model, rm, x, fine_cpu, memory_prompt_embeds, frame_prompt_embeds, image_newline,
-                                  with_frames, out):
-    """Training-mode tail of video_memory_tokens (llava_arch.py:545-554,620-629): the fuser MLP runs as HIP autograd
-    Functions; the type-embedding adds and the concatenation are torch ops so that autograd routes the gradients of
+                                  with_frames, out, layout="one_token"):
+    """Training-mode tail of video_memory_tokens (llava_arch.py:545-554,567-634): the fuser MLP runs as HIP autograd
+    Functions; the type-embedding adds, the layout and the concatenation are torch ops so that autograd routes the gradients of
     token_type_embedding, the prompt embeddings and image_newline exactly as in the reference."""
     from .. import _autograd as ag
     P, D = x.shape[1], x.shape[2]
@@ -281,19 +372,22 @@ def _video_memory_tokens_autograd(model, rm, x, fine_cpu, memory_prompt_embeds, 
     # engine-mode cache entries are ring views: torch.cat copies them (the graph must not alias the ring)
     mem = torch.cat(rm.memory_cache, dim=0)                                               # :545
     fused = ag.fuser_mlp(model.memory_fuser, mem, temb[0]).reshape(-1, D)                  # :546-553
-    nl = image_newline.to(device=x.device, dtype=dt).reshape(1, D)
-    parts = [memory_prompt_embeds.to(dt), fused, nl]
+    _require_newline(image_newline, layout)
+    nl = None if layout == "no_token" else image_newline.to(device=x.device, dtype=dt).reshape(1, D)
+    mem_block = _lay_out_block(fused, nl, layout, P)                                       # :567-634
+    parts = [memory_prompt_embeds.to(dt), mem_block]
     n = len(rm.memory_cache)
     R = rm.num_memory_tokens * P
     if with_frames:
         fine = x[_device_indices(fine_cpu, x.device)] + temb[1].to(dt)                     # :513-524,554
-        parts += [frame_prompt_embeds.to(dt), fine.reshape(-1, D), nl]
+        parts += [frame_prompt_embeds.to(dt), _lay_out_block(fine.reshape(-1, D), nl, layout, P)]
     tokens = torch.cat(parts, dim=0)
     if out is not None:
         raise capi.MavlmError("video_memory_tokens: `out=` is an inference-path feature (no autograd through a "
                               "caller-owned buffer)")
     mp_rows = memory_prompt_embeds.shape[0]
-    info = {"num_memories": n, "pe_frames": x, "fine_idx": fine_cpu, "memory_rows": (mp_rows, mp_rows + n * R)}
+    info = {"num_memories": n, "pe_frames": x, "fine_idx": fine_cpu,
+            "memory_rows": (mp_rows, mp_rows + (mem_block.shape[0] if layout_period(layout, P) else n * R))}
     return tokens, info
 
 
@@ -320,6 +414,7 @@ class MemoryPathPool:
 
     usage:  pool = MemoryPathPool(model, 2)
             outs = pool.run([(frames0, idx0), (frames1, idx1), ...], mem_prompt, frame_prompt, newline)
+    (`layout=`: the token layout of every block, as video_memory_tokens)
 
     `batch` > 1 (round 3): each stream steps `batch` videos TOGETHER as a row batch (`BatchedProjector`: the memory rows of
     the videos stacked into every weight-shared GEMM / LayerNorm launch) instead of one.  Consecutive videos of equal length
@@ -344,7 +439,8 @@ class MemoryPathPool:
         self.streams = None
 
     @torch.no_grad()           # inference feature: the replicas' FIFOs are ring views, not autograd tensors
-    def run(self, videos, memory_prompt_embeds, frame_prompt_embeds, image_newline, with_frames: bool = True):
+    def run(self, videos, memory_prompt_embeds, frame_prompt_embeds, image_newline, with_frames: bool = True,
+            layout: str = "one_token"):
         if self.streams is None:
             self.streams = _side_streams(torch.cuda.current_device(), len(self.slots))
         cur = torch.cuda.current_stream()
@@ -366,7 +462,8 @@ class MemoryPathPool:
                 k = g % len(self.bslots)
                 with torch.cuda.stream(self.streams[k]):
                     toks = video_memory_tokens_batched(self.model, self.bslots[k], [v[0] for v in grp], grp[0][1],
-                                                       memory_prompt_embeds, frame_prompt_embeds, image_newline, with_frames)[0]
+                                                       memory_prompt_embeds, frame_prompt_embeds, image_newline, with_frames,
+                                                       layout=layout)[0]
                     for j, v in enumerate(grp):
                         outs[i + j] = toks[j]
                         v[0].record_stream(self.streams[k])
@@ -377,7 +474,7 @@ class MemoryPathPool:
             k = j % len(self.slots)
             with torch.cuda.stream(self.streams[k]):
                 outs[i] = video_memory_tokens(self.slots[k], frames, idx_cpu, memory_prompt_embeds, frame_prompt_embeds,
-                                              image_newline, with_frames)[0]
+                                              image_newline, with_frames, layout=layout)[0]
                 frames.record_stream(self.streams[k])
         for st in self.streams:
             cur.wait_stream(st)
@@ -393,7 +490,7 @@ class GraphedVideoMemory:
     usage:  g = GraphedVideoMemory(model, T=256, frame_idx_cpu=idx)        # captures on the current device
             tokens = g(frames, mem_prompt, frame_prompt, newline)          # copies into the static inputs, replays
     The returned tensor is the graph's static output buffer (valid until the next call).  A new shape (T, indices,
-    with_frames) needs a new instance.
+    with_frames, layout) needs a new instance: the token layout is baked into the captured launches.
 
     A graph replays the device pointers it was captured with: the engine's workspace and FIFO ring, its packed weight copies
     (fp32 biases / LayerNorm affines, concatenated K/V weights), the PE table, the fuser and token-type parameters.  The instance
@@ -404,8 +501,10 @@ class GraphedVideoMemory:
     so by itself)."""
 
     @torch.no_grad()
-    def __init__(self, model, T: int, frame_idx_cpu: torch.Tensor, with_frames: bool = True, slot=None):
+    def __init__(self, model, T: int, frame_idx_cpu: torch.Tensor, with_frames: bool = True, slot=None,
+                 layout: str = "one_token"):
         rm = model.recurrent_memory_transformer
+        self.layout = layout
         self.view = slot if slot is not None else _ReplicaView(model, rm.spawn_replica())
         self.idx = frame_idx_cpu.clone()
         self.with_frames = with_frames
@@ -421,11 +520,11 @@ class GraphedVideoMemory:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            video_memory_tokens(self.view, self.x, self.idx, self.mp, self.fp, self.nl, with_frames)
+            video_memory_tokens(self.view, self.x, self.idx, self.mp, self.fp, self.nl, with_frames, layout=layout)
         torch.cuda.current_stream().wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.out, _ = video_memory_tokens(self.view, self.x, self.idx, self.mp, self.fp, self.nl, with_frames)
+            self.out, _ = video_memory_tokens(self.view, self.x, self.idx, self.mp, self.fp, self.nl, with_frames, layout=layout)
         # what the module's host-side state looks like after this video (ring views of the FIFO, scores of the chunks): a replay
         # only re-runs the device work, so __call__ puts these back - `recurrent_memory_transformer.memory_cache` read after a
         # replayed forward is the replayed video's cache, as after an eager forward (matters when the slot is the model itself)
@@ -477,7 +576,9 @@ class GraphedVideoMemory:
         self.x.copy_(frames)
         self.mp.copy_(memory_prompt_embeds)
         self.fp.copy_(frame_prompt_embeds)
-        self.nl.copy_(image_newline)
+        if self.layout != "no_token":
+            _require_newline(image_newline, self.layout)
+            self.nl.copy_(image_newline)
         self.graph.replay()
         self.view.recurrent_memory_transformer._memory_cache = list(self._cache)
         return self.out
@@ -573,9 +674,8 @@ class LlavaMetaForCausalLM:
                                       "only batch size of 1'; a second video fails the reference's patch-grid assert, :636)")
         # non-video entries beside the video are encoded and then DROPPED by the reference (:487-490, 556): dropped here too
         images = [images[vids[0]]]
-        if getattr(self.config, "mm_newline_position", "one_token") != "one_token" or \
-                "unpad" not in getattr(self.config, "mm_patch_merge_type", "flat"):
-            raise NotImplementedError("memory path: mm_newline_position='one_token' with an *_unpad merge type only")
+        layout = token_layout(self.config)                                                      # :562-634
+        _require_newline(getattr(model, "image_newline", None), layout)                         # AttributeError, as the reference
         video = images[0]
         idx_cpu = sample_frame_indices(video.shape[0])                                          # :437-451
         feats = self.encode_images(video[idx_cpu.to(video.device)])                             # :457-481
@@ -593,15 +693,15 @@ class LlavaMetaForCausalLM:
         # (batch 1, one image placeholder, llava_arch.py:436): the final [1, L, D] buffer is allocated once and the
         # HIP path writes the video block straight into it; everything else goes through the general splice.
         direct = self._direct_emit(model, pooled, idx_cpu, mem_prompt, frame_prompt, not drop, input_ids, position_ids,
-                                   attention_mask, past_key_values, labels)
+                                   attention_mask, past_key_values, labels, layout)
         if direct is not None:
             return direct
-        tokens = self._video_tokens(model, pooled, idx_cpu, mem_prompt, frame_prompt, not drop)
+        tokens = self._video_tokens(model, pooled, idx_cpu, mem_prompt, frame_prompt, not drop, layout=layout)
         return splice_into_text(self, model, [tokens], input_ids, position_ids, attention_mask, past_key_values, labels)
 
     # -- hipGraph replay for repeated video shapes (round 4) -------------------------------------------------------------
     def enable_memory_graphs(self, capacity: int = 4):
-        """Inference: serve videos of a shape seen before ((frames, frame indices, with_frames) of the sampled video) by replaying
+        """Inference: serve videos of a shape seen before ((frames, frame indices, with_frames, token layout) of the sampled video) by replaying
         a captured hipGraph of the whole per-video launch sequence (`GraphedVideoMemory` on the model's own engine: PE add,
         every chunk step, fuser + emit) instead of ~45 launches; the first occurrence of a shape runs eagerly, the second
         captures.  Bit-identical to the eager path (`test_graph_capture_replay_bit_identical`); a graph captured over weights or an
@@ -613,14 +713,18 @@ class LlavaMetaForCausalLM:
         self._mem_graphs = {}
         self._mem_graph_seen = {}
 
-    def _video_tokens(self, model, pooled, idx_cpu, mem_prompt, frame_prompt, with_frames, out=None):
+    def _video_tokens(self, model, pooled, idx_cpu, mem_prompt, frame_prompt, with_frames, out=None, layout="one_token"):
         """video_memory_tokens, through the graph cache when it applies (inference, shape seen before)"""
         cap = getattr(self, "_mem_graph_capacity", 0)
-        if (cap <= 0 or path_wants_grad(model, mem_prompt, frame_prompt, getattr(model, "image_newline", None))
+        newline = getattr(model, "image_newline", None)
+        if (cap <= 0 or path_wants_grad(model, mem_prompt, frame_prompt, newline)
                 or torch.cuda.is_current_stream_capturing() or model.recurrent_memory_transformer.training
                 or getattr(model.recurrent_memory_transformer, "record_attention_maps", False)):      # (maps: eager steps only)
-            return video_memory_tokens(model, pooled, idx_cpu, mem_prompt, frame_prompt, model.image_newline, with_frames, out=out)[0]
+            return video_memory_tokens(model, pooled, idx_cpu, mem_prompt, frame_prompt, newline, with_frames, out=out,
+                                       layout=layout)[0]
         key = (pooled.shape[0], tuple(int(i) for i in idx_cpu.tolist()), bool(with_frames), pooled.dtype, pooled.device.index)
+        if layout != "one_token":
+            key += (layout,)                               # (a graph is captured for ONE layout; the default keeps the plain key)
         g = self._mem_graphs.pop(key, None)
         if g is not None and g.stale() is not None:
             g = None                                       # captured over state that has changed since: dropped, re-captured
@@ -630,22 +734,22 @@ class LlavaMetaForCausalLM:
             if len(self._mem_graph_seen) > 64:
                 self._mem_graph_seen.pop(next(iter(self._mem_graph_seen)))
             if n < 2:
-                return video_memory_tokens(model, pooled, idx_cpu, mem_prompt, frame_prompt, model.image_newline, with_frames,
-                                           out=out)[0]
+                return video_memory_tokens(model, pooled, idx_cpu, mem_prompt, frame_prompt, newline, with_frames,
+                                           out=out, layout=layout)[0]
             with torch.no_grad():
-                g = GraphedVideoMemory(model, pooled.shape[0], idx_cpu, with_frames, slot=model)
+                g = GraphedVideoMemory(model, pooled.shape[0], idx_cpu, with_frames, slot=model, layout=layout)
             while len(self._mem_graphs) >= cap:
                 self._mem_graphs.pop(next(iter(self._mem_graphs)))
         self._mem_graphs[key] = g                          # (re-inserted last: most recently used)
         with torch.no_grad():
-            tokens = g._replay(pooled, mem_prompt, frame_prompt, model.image_newline)     # (validated above / just captured)
+            tokens = g._replay(pooled, mem_prompt, frame_prompt, newline)                 # (validated above / just captured)
         if out is not None:
             out.copy_(tokens)
             return out
         return tokens.clone()                              # (the graph's static buffer is overwritten by its next replay)
 
     def _direct_emit(self, model, pooled, idx_cpu, mem_prompt, frame_prompt, with_frames, input_ids, position_ids,
-                     attention_mask, past_key_values, labels):
+                     attention_mask, past_key_values, labels, layout="one_token"):
         if input_ids.shape[0] != 1:
             return None
         if path_wants_grad(model, mem_prompt, frame_prompt, getattr(model, "image_newline", None)):
@@ -658,7 +762,7 @@ class LlavaMetaForCausalLM:
         p = pos[0]
         rm = model.recurrent_memory_transformer
         rows = video_token_rows(pooled.shape[0], rm.num_memory_tokens, rm.patch_size, with_frames,
-                                cache_cap=getattr(rm.config, "cache_cap", 10))
+                                cache_cap=getattr(rm.config, "cache_cap", 10), layout=layout)
         n_text = ids.shape[0] - 1
         total = n_text + rows
         max_tok = getattr(self.config, "tokenizer_model_max_length", None)
@@ -668,7 +772,7 @@ class LlavaMetaForCausalLM:
         emb = torch.empty((1, total, pooled.shape[-1]), device=pooled.device, dtype=pooled.dtype)
         emb[0, :p] = text[:p].to(emb.dtype)
         emb[0, p + rows:] = text[p:].to(emb.dtype)
-        self._video_tokens(model, pooled, idx_cpu, mem_prompt, frame_prompt, with_frames, out=emb[0, p:p + rows])
+        self._video_tokens(model, pooled, idx_cpu, mem_prompt, frame_prompt, with_frames, out=emb[0, p:p + rows], layout=layout)
         if text.dtype != emb.dtype:
             emb = emb.to(text.dtype)
         out_labels = None
