@@ -333,6 +333,19 @@ int mavlm_attention_hd_plan_info(int32_t R, int32_t S, int32_t H, int32_t head_d
 int mavlm_attention_hd_ws(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, void* O,
                           int32_t ldo, float* lse2, int32_t R, int32_t S, int32_t H, int32_t head_dim, float scale, float* ws,
                           int64_t ws_floats, int32_t dtype, void* stream);
+/* Row-batched forward: ONE launch serves nb independent videos (the training path of a row batch; the fused step does the
+ * same inside mavlm_step_batch).  H counts the heads of ALL videos (H % nb == 0, Hv = H / nb per video); Q / O hold the nb x R
+ * query rows video after video ([nb*R, >= Hv*w], w = 128 for head_dim <= 128 - narrower heads zero-padded - or 448); video b's S
+ * keys start b * kv_bstride elements into K and V; lse2 is [H, R] with h = b*Hv + head.  The schedule is the one the step
+ * takes for a row batch - the stream-K plan over all H (video, head) pairs where it applies, never the split-KV form of the
+ * small grids (a single video, nb = 1, takes that one as mavlm_attention_ws does) - so a batched operator call gives the bits of
+ * mavlm_step_batch.  ws: mavlm_attention_batch_ws_floats(...) floats (0 = plain grid).  All arguments are checked before anything
+ * is enqueued: MAVLM_E_ARG for a null pointer, nb < 1, nb > MAVLM_MAX_BATCH, H % nb != 0, bad strides or too small a
+ * workspace; MAVLM_E_SHAPE for a head_dim other than <= 128 or 448. */
+int64_t mavlm_attention_batch_ws_floats(int32_t R, int32_t S, int32_t H, int32_t nb, int32_t head_dim);
+int mavlm_attention_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, void* O,
+                          int32_t ldo, float* lse2, int32_t R, int32_t S, int32_t H, float scale, float* ws,
+                          int64_t ws_floats, int32_t nb, int64_t kv_bstride, int32_t head_dim, int32_t dtype, void* stream);
 int mavlm_attention_colsum_hd(const void* Q, int32_t ldq, const void* K, int32_t ldk, const float* lse2, float* part,
                               int32_t R, int32_t S, int32_t H, int32_t head_dim, float scale, int32_t dtype, void* stream);
 /* part[H,S] fp32 = column sums over queries of the normalised probabilities.  MemoryController.py:135
@@ -387,6 +400,22 @@ int mavlm_attention_bwd_hd(const void* Q, int32_t ldq, const void* K, int32_t ld
                            int32_t ldo, const void* dO, int32_t lddo, const float* lse2, float* delta, void* dQ,
                            int32_t lddq, void* dK, int32_t lddk, void* dV, int32_t lddv, int32_t R, int32_t S, int32_t H,
                            int32_t head_dim, float scale, int32_t dtype, void* stream);
+/* Row-batched backward (head columns of 128, and of 448): the gradients of mavlm_attention_batch's nb videos in one launch
+ * per output.  Layout as there: H heads of all videos, Q / O / dO / dQ [nb*R, ...] video after video, lse2 / delta [H, R];
+ * video b's keys start b * kv_bstride elements into K and V, its key gradients b * dkv_bstride elements into dK and dV (both
+ * strides in elements; any destination rows between two videos are left untouched).  Every output row has one owner and no
+ * atomics are used: the result equals nb single-video calls bit for bit.  Checks before anything is enqueued: MAVLM_E_ARG for
+ * a null required pointer, nb < 1, nb > MAVLM_MAX_BATCH, H % nb != 0, misaligned or too narrow operands; MAVLM_E_SHAPE for a
+ * head_dim other than 448 (the _hd form). */
+int mavlm_attention_bwd_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, const void* O,
+                              int32_t ldo, const void* dO, int32_t lddo, const float* lse2, float* delta, void* dQ,
+                              int32_t lddq, void* dK, int32_t lddk, void* dV, int32_t lddv, int32_t R, int32_t S, int32_t H,
+                              float scale, int32_t nb, int64_t kv_bstride, int64_t dkv_bstride, int32_t dtype, void* stream);
+int mavlm_attention_bwd_hd_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv,
+                                 const void* O, int32_t ldo, const void* dO, int32_t lddo, const float* lse2, float* delta,
+                                 void* dQ, int32_t lddq, void* dK, int32_t lddk, void* dV, int32_t lddv, int32_t R, int32_t S,
+                                 int32_t H, int32_t head_dim, float scale, int32_t nb, int64_t kv_bstride, int64_t dkv_bstride,
+                                 int32_t dtype, void* stream);
 /* C[M,N] 16-bit = A[M,K] . W[N,K]^T, contraction split over `splits` workgroup planes; ws = splits*M*N fp32;
  * zero_bias = N fp32 zeros.  For dW = dY^T X, whose contraction runs over all rows of the activations. */
 int mavlm_linear_splitk(const void* A, int32_t lda, const void* W, int32_t ldw, void* C, int32_t M, int32_t N, int32_t K,

@@ -16,6 +16,7 @@ from . import _capi as capi
 from . import _ops as ops
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
+ACT_GELU_FUSED = 3      # GELU with the forward value of the inference epilogue (LinearFn)
 
 
 def _c(t):
@@ -60,6 +61,13 @@ class LinearFn(torch.autograd.Function):
             pre = ops.linear(x, w, b32, capi.EPI_BIAS)
             y = ops.act(ops.ACT_GELU, pre)
             ctx.save_for_backward(x, w, pre)
+        elif act == ACT_GELU_FUSED:
+            # the forward value is the inference epilogue's - gelu of the fp32 accumulator, one rounding - at the price of a
+            # second GEMM for the 16-bit pre-activation the derivative is taken at: bit-identical activations to inference
+            pre = ops.linear(x, w, b32, capi.EPI_BIAS)
+            y = ops.linear(x, w, b32, capi.EPI_GELU)
+            ctx.save_for_backward(x, w, pre)
+            act = ACT_GELU
         elif act == ACT_RELU:
             y = ops.linear(x, w, b32, capi.EPI_RELU)
             ctx.save_for_backward(x, w, y)
@@ -117,14 +125,19 @@ class DenseResidualNormFn(torch.autograd.Function):
 
 class AttentionFn(torch.autograd.Function):
     """ctx = softmax(q k^T * scale) v per head (MemoryController.py:51-54), heads of 128 columns (narrower heads are
-    zero-padded by the caller).  Saves O and the log-sum-exp; the backward recomputes the probabilities per tile."""
+    zero-padded by the caller).  Saves O and the log-sum-exp; the backward recomputes the probabilities per tile.
+    `nb` > 1: a row batch - q holds the query rows of nb videos one after the other, k / v are [nb, S, W] views (`heads` per
+    video); forward and backward are ONE launch each over the (video, head) pairs, on the schedule of `mavlm_step_batch`."""
 
     @staticmethod
-    def forward(ctx, q, k, v, heads, scale, head_dim=128, plain=False):
+    def forward(ctx, q, k, v, heads, scale, head_dim=128, plain=False, nb=1):
         q, k, v = q.detach(), k.detach(), v.detach()
-        o, lse = ops.attention(q, k, v, heads, want_lse=True, scale=scale, head_dim=head_dim, plain=plain)
+        if nb > 1:
+            o, lse = ops.attention_batch(q, k, v, heads, nb, want_lse=True, scale=scale, head_dim=head_dim)
+        else:
+            o, lse = ops.attention(q, k, v, heads, want_lse=True, scale=scale, head_dim=head_dim, plain=plain)
         ctx.save_for_backward(q, k, v, o, lse)
-        ctx.heads, ctx.scale, ctx.head_dim = heads, scale, head_dim
+        ctx.heads, ctx.scale, ctx.head_dim, ctx.nb = heads, scale, head_dim, nb
         ctx.mark_non_differentiable(lse)
         return o, lse
 
@@ -132,11 +145,16 @@ class AttentionFn(torch.autograd.Function):
     def backward(ctx, do, _dlse):
         q, k, v, o, lse = ctx.saved_tensors
         n = ctx.needs_input_grad
-        if ctx.head_dim == 128:
+        if ctx.nb > 1:
+            if ctx.head_dim not in (128, 448):
+                raise capi.MavlmError(f"row-batched attention backward: head width {ctx.head_dim} (128 or 448)")
+            dq, dk, dv = ops.attention_bwd_batch(q, k, v, o, _c(do), lse, ctx.heads, ctx.nb, n[0], n[1], n[2], scale=ctx.scale,
+                                                 head_dim=ctx.head_dim)
+        elif ctx.head_dim == 128:
             dq, dk, dv = ops.attention_bwd(q, k, v, o, _c(do), lse, ctx.heads, n[0], n[1], n[2], scale=ctx.scale)
         else:       # wide heads (448): one head's scores at a time, every product a GEMM (ops.attention_bwd_wide)
             dq, dk, dv = ops.attention_bwd_wide(q, k, v, o, _c(do), lse, ctx.heads, ctx.head_dim, ctx.scale, n[0], n[1], n[2])
-        return dq, dk, dv, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None
 
 
 def head_width(hd):
@@ -173,18 +191,23 @@ def packed_kv_params(attns):
     return torch.cat(ws, dim=0), torch.cat(bs, dim=0)
 
 
-def project_kv(attns, x):
+def project_kv(attns, x, nb=1):
     """K/V of `x` for all `attns` in ONE GEMM (as mavlm_step does): returns [(k, v), ...] column views of the packed
-    [rows, 2*len(attns)*H*128] output."""
+    [rows, 2*len(attns)*H*128] output.  `nb` > 1: `x` holds the rows of nb videos one after the other (row-independent: the
+    same GEMM over the stacked rows); the views are [nb, rows / nb, H*128]."""
     w, b = packed_kv_params(attns)
     kv = LinearFn.apply(x, w.to(x.dtype), b, ACT_NONE)
     Dp = attns[0].num_attention_heads * head_width(attns[0].attention_head_size)
+    if nb > 1:
+        kv = kv.view(nb, kv.shape[0] // nb, kv.shape[1])
+        return [(kv[:, :, (2 * i) * Dp:(2 * i + 1) * Dp], kv[:, :, (2 * i + 1) * Dp:(2 * i + 2) * Dp]) for i in range(len(attns))]
     return [(kv[:, (2 * i) * Dp:(2 * i + 1) * Dp], kv[:, (2 * i + 1) * Dp:(2 * i + 2) * Dp]) for i in range(len(attns))]
 
 
-def attention_block(attn, q_in, k, v, want_stats=False, patches_per_frame=196):
+def attention_block(attn, q_in, k, v, want_stats=False, patches_per_frame=196, nb=1):
     """`Attention.forward` (MemoryController.py:47-56) on a 2-D [rows, D] query input and already projected K/V
-    (padded-head layout; may be column views); returns (out, (q, k, lse) | None)."""
+    (padded-head layout; may be column views); returns (out, (q, k, lse) | None).  `nb` > 1: the stacked rows of nb videos
+    and [nb, S, W] keys / values - every GEMM and LayerNorm runs once over all rows, the attention over (video, head) pairs."""
     H = attn.num_attention_heads
     hd = attn.attention_head_size
     if hd > 128 and hd != 448:
@@ -195,7 +218,7 @@ def attention_block(attn, q_in, k, v, want_stats=False, patches_per_frame=196):
                        ACT_NONE)
     # (the fused step's last formation layer carries the frame scores on the SAME schedule as every other attention of
     # the shape - round 3 - so there is no special case here: `ops.attention` takes that schedule)
-    ctxv, lse = AttentionFn.apply(q, k, v, H, scale, head_width(hd), False)
+    ctxv, lse = AttentionFn.apply(q, k, v, H, scale, head_width(hd), False, nb)
     d = attn.residual
     out = DenseResidualNormFn.apply(ctxv, pad_heads_in(d.dense.weight, H, hd).to(dt), d.dense.bias, q_in,
                                     d.layernorm.weight, d.layernorm.bias, d.layernorm.eps)
@@ -211,11 +234,13 @@ def mlp_block(layer, a):
                                      d.layernorm.eps)
 
 
-def fuser_mlp(fuser, x, type_row=None):
+def fuser_mlp(fuser, x, type_row=None, fused_gelu=False):
     """memory_fuser = Linear GELU Linear (llava_arch.py:132-136,546); `type_row` (token_type_embedding row 0) rides in
-    the second bias so the add costs no extra rounding (as the inference epilogue, :548-553)."""
+    the second bias so the add costs no extra rounding (as the inference epilogue, :548-553).  `fused_gelu`: the forward
+    value of the inference path's GELU epilogue (ACT_GELU_FUSED: the fused tokens are then inference's bits)."""
     shp = x.shape
-    u = LinearFn.apply(x.reshape(-1, shp[-1]), fuser[0].weight.to(x.dtype), fuser[0].bias, ACT_GELU)
+    u = LinearFn.apply(x.reshape(-1, shp[-1]), fuser[0].weight.to(x.dtype), fuser[0].bias,
+                       ACT_GELU_FUSED if fused_gelu else ACT_GELU)
     b2 = fuser[2].bias.float()
     if type_row is not None:
         b2 = b2 + type_row.float()

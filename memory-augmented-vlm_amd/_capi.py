@@ -12,6 +12,7 @@ MAX_DEPTH = 8
 BF16, F16 = 0, 1
 EPI_BIAS, EPI_RELU, EPI_GELU, EPI_RES_F32, EPI_F32 = 0, 1, 2, 3, 4
 E_ARG, E_SHAPE, E_STATE = -1, -2, -3
+MAX_BATCH = 64         # include/mavlm.h MAVLM_MAX_BATCH
 # MAVLM_LAYOUT_*: where image_newline rows go in the video token block, by the names model/llava_arch.py token_layout() returns
 LAYOUT_ONE, LAYOUT_NONE, LAYOUT_FRAME, LAYOUT_GRID = 0, 1, 2, 3
 LAYOUTS = {"one_token": LAYOUT_ONE, "no_token": LAYOUT_NONE, "frame": LAYOUT_FRAME, "grid": LAYOUT_GRID}
@@ -108,6 +109,13 @@ SIGNATURES = {
                                       i32, i32, i32, C.c_float, i32, vp]),
     "mavlm_attention_bwd_hd": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32,
                                          i32, i32, i32, i32, C.c_float, i32, vp]),
+    "mavlm_attention_batch_ws_floats": (C.c_int64, [i32, i32, i32, i32, i32]),
+    "mavlm_attention_batch": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, C.c_float, vp, C.c_int64, i32,
+                                        C.c_int64, i32, i32, vp]),
+    "mavlm_attention_bwd_batch": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32,
+                                            i32, i32, i32, C.c_float, i32, C.c_int64, C.c_int64, i32, vp]),
+    "mavlm_attention_bwd_hd_batch": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32,
+                                               i32, i32, i32, i32, C.c_float, i32, C.c_int64, C.c_int64, i32, vp]),
     "mavlm_linear_splitk": (C.c_int, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp]),
     "mavlm_layernorm_bwd_ws_floats": (C.c_int64, [i32]),
     "mavlm_layernorm_bwd": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, C.c_float, i32, vp]),

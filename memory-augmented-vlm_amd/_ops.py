@@ -302,6 +302,92 @@ def attention_bwd(q, k, v, o, do, lse2, heads, need_dq=True, need_dk=True, need_
     return dq, dk, dv
 
 
+def _kv_batch(t, nb, what):
+    """[nb, S, W] view of the keys / values of a row batch (a column slice of a wider buffer is fine; one stride between the
+    videos): returns (S, row stride, video stride) in elements."""
+    if t.dim() != 3 or t.shape[0] != nb or t.stride(2) != 1:
+        raise capi.MavlmError(f"{what}: expected a [nb, S, W] view with unit inner stride")
+    return t.shape[1], t.stride(1), (t.stride(0) if nb > 1 else t.shape[1] * t.stride(1))
+
+
+def attention_batch(q, k, v, heads, nb, want_lse=False, head_dim=128, scale=None):
+    """`attention` for nb videos in ONE launch (`mavlm_attention_batch`): q [nb*R, >=heads*w] holds the videos' query rows one
+    after the other, k / v are [nb, S, >=heads*w] views (w = 128, or 448 for the wide heads), `heads` per video.  The schedule
+    is the one `mavlm_step_batch` takes for the stacked grid: same bits as the batched inference step.
+    Returns (ctx [nb*R, heads*w], lse2 [nb*heads, R] fp32 | None)."""
+    _need_gpu(q, k, v)
+    RB, _, ldq = _rows(q)
+    S, ldk, kbs = _kv_batch(k, nb, "attention_batch")
+    S2, ldv, vbs = _kv_batch(v, nb, "attention_batch")
+    hw = 448 if head_dim == 448 else 128
+    W = heads * hw
+    if RB % nb or S2 != S or vbs != kbs or q.shape[1] < W or k.shape[2] < W or v.shape[2] < W or k.dtype != q.dtype \
+            or v.dtype != q.dtype:
+        raise capi.MavlmError("attention_batch: operand mismatch (stacked query rows, K / V with one video stride)")
+    R, H = RB // nb, heads * nb
+    lib = capi.lib()
+    out = torch.empty((RB, W), device=q.device, dtype=q.dtype)
+    lse = torch.empty((H, R), device=q.device, dtype=torch.float32) if want_lse else None
+    nws = int(lib.mavlm_attention_batch_ws_floats(R, S, H, nb, head_dim))
+    ws = torch.empty((nws,), device=q.device, dtype=torch.float32) if nws else None
+    capi.check(lib.mavlm_attention_batch(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), out.stride(0),
+                                         lse.data_ptr() if want_lse else 0, R, S, H,
+                                         1.0 / math.sqrt(float(head_dim)) if scale is None else float(scale),
+                                         ws.data_ptr() if nws else 0, nws, nb, kbs, head_dim, dtype_code(q.dtype), stream_ptr()),
+               "mavlm_attention_batch")
+    return out, lse
+
+
+def attention_bwd_batch(q, k, v, o, do, lse2, heads, nb, need_dq=True, need_dk=True, need_dv=True, scale=None, head_dim=128,
+                        dk_out=None, dv_out=None):
+    """Gradients of `attention_batch` in one launch per output (`mavlm_attention_bwd_batch`; head_dim 448 is routed to
+    `mavlm_attention_bwd_hd_batch`): bit-identical to nb single-video `attention_bwd` calls.  Returns (dq [nb*R, W] | None,
+    dk | None, dv | None), dk / dv [nb, S, W]; `dk_out` / `dv_out`: caller-owned [nb, S, W] views to write instead (same
+    strides for both; rows between the videos are left untouched)."""
+    _need_gpu(q, k, v, o, do, lse2, dk_out, dv_out)
+    RB, _, ldq = _rows(q)
+    S, ldk, kbs = _kv_batch(k, nb, "attention_bwd_batch")
+    S2, ldv, vbs = _kv_batch(v, nb, "attention_bwd_batch")
+    _, _, ldo = _rows(o)
+    do = do if do.stride(-1) == 1 else do.contiguous()
+    _, _, lddo = _rows(do)
+    hw = 448 if head_dim == 448 else 128
+    W = heads * hw
+    H = heads * nb
+    if RB % nb or S2 != S or vbs != kbs or o.shape != (RB, W) or do.shape != (RB, W) or lse2.shape != (H, RB // nb) \
+            or lse2.dtype != torch.float32 or not lse2.is_contiguous() or do.dtype != q.dtype:
+        raise capi.MavlmError("attention_bwd_batch: operand mismatch")
+    R = RB // nb
+    dq = torch.empty((RB, W), device=q.device, dtype=q.dtype) if need_dq else None
+    dk = (dk_out if dk_out is not None else torch.empty((nb, S, W), device=q.device, dtype=q.dtype)) if need_dk else None
+    dv = (dv_out if dv_out is not None else torch.empty((nb, S, W), device=q.device, dtype=q.dtype)) if need_dv else None
+    lddk = lddv = W
+    dbs = S * W
+    geo = [_kv_batch(t, nb, "attention_bwd_batch") for t in (dk, dv) if t is not None]
+    if geo:
+        if any(g[0] != S or g[2] != geo[0][2] for g in geo) or any(t is not None and (t.shape[2] != W or t.dtype != q.dtype)
+                                                                  for t in (dk, dv)):
+            raise capi.MavlmError("attention_bwd_batch: dk / dv destinations must be [nb, S, W] views with one video stride")
+        dbs = geo[0][2]
+        lddk = dk.stride(1) if dk is not None else W
+        lddv = dv.stride(1) if dv is not None else W
+    delta = torch.empty((H, R), device=q.device, dtype=torch.float32)
+    p = lambda t: t.data_ptr() if t is not None else 0
+    sc = 1.0 / math.sqrt(float(head_dim)) if scale is None else float(scale)
+    lib = capi.lib()
+    if hw == 448:
+        capi.check(lib.mavlm_attention_bwd_hd_batch(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo,
+                                                    do.data_ptr(), lddo, lse2.data_ptr(), delta.data_ptr(), p(dq), W, p(dk),
+                                                    lddk, p(dv), lddv, R, S, H, head_dim, sc, nb, kbs, dbs,
+                                                    dtype_code(q.dtype), stream_ptr()), "mavlm_attention_bwd_hd_batch")
+    else:
+        capi.check(lib.mavlm_attention_bwd_batch(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo,
+                                                 do.data_ptr(), lddo, lse2.data_ptr(), delta.data_ptr(), p(dq), W, p(dk), lddk,
+                                                 p(dv), lddv, R, S, H, sc, nb, kbs, dbs, dtype_code(q.dtype), stream_ptr()),
+                   "mavlm_attention_bwd_batch")
+    return dq, dk, dv
+
+
 def transpose(x, pad_to=64, out_rows=None):
     """[rows, cols] 16-bit -> [cols, roundup(rows, 64)] with a zero-filled pad (the K-contiguous operand form of
     the contract-over-rows products).  `out_rows` > cols: the result gets that many rows, the extra ones zero (an

@@ -44,7 +44,8 @@ __global__ __launch_bounds__(256, (MODE == 3 ? 1 : 2)) void attn_bwd_kernel(cons
                                                           const float* __restrict__ lse2, const float* __restrict__ delta,
                                                           uint16_t* __restrict__ Out, int ldo, int NX, int NY, int R,
                                                           int H, float c, float out_scale,
-                                                          uint16_t* __restrict__ Out2 = nullptr, int ldo2 = 0) {
+                                                          uint16_t* __restrict__ Out2, int ldo2, int Hv,
+                                                          long long kvb, long long okvb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -53,17 +54,29 @@ __global__ __launch_bounds__(256, (MODE == 3 ? 1 : 2)) void attn_bwd_kernel(cons
   const int x0 = (blockIdx.x / H) * 128 + wave * 32;
   const int r = lane & 31, hh = lane >> 5;
   const int nt = (NY + BKT - 1) / BKT;
+  // row batch: H counts the heads of all videos, Hv per video.  Head h belongs to video vb and sits at the columns of head hc;
+  // every operand moves to that video's rows - the queries' side is stacked (R rows per video), the keys' side lies kvb
+  // elements apart (the key gradients okvb) - so that all row indices, the descriptors' ends and the 32-bit offsets below
+  // stay those of ONE video.  (A single video: vb = 0, hc = h.)
+  const int vb = h / Hv, hc = h - vb * Hv;
+  if (MODE == 0) {
+    X += (size_t)vb * NX * ldx; X2 += (size_t)vb * NX * ldx2; Y += vb * kvb; Y2 += vb * kvb; Out += (size_t)vb * NX * ldo;
+  } else {
+    X += vb * kvb; Y += (size_t)vb * NY * ldy; Y2 += (size_t)vb * NY * ldy2; Out += vb * okvb;
+    if (MODE != 2) X2 += vb * kvb;
+    if (MODE == 3) Out2 += vb * okvb;
+  }
 
   // ---- stationary fragments (B operands): lane holds X[x0+r][h*128 + 16ks + 8hh + 0..7]
   typename T::vec8 xf[8], x2f[8];
   int xrow = x0 + r;
   xrow = xrow < NX ? xrow : NX - 1;
   {
-    const uint16_t* xp = X + (size_t)xrow * ldx + h * BHD + 8 * hh;
+    const uint16_t* xp = X + (size_t)xrow * ldx + hc * BHD + 8 * hh;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) xf[ks] = *(const typename T::vec8*)(xp + 16 * ks);
     if (MODE != 2) {
-      const uint16_t* xp2 = X2 + (size_t)xrow * ldx2 + h * BHD + 8 * hh;
+      const uint16_t* xp2 = X2 + (size_t)xrow * ldx2 + hc * BHD + 8 * hh;
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks) x2f[ks] = *(const typename T::vec8*)(xp2 + 16 * ks);
     }
@@ -89,8 +102,8 @@ __global__ __launch_bounds__(256, (MODE == 3 ? 1 : 2)) void attn_bwd_kernel(cons
     return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes),
                                              0x00020000);
   };
-  const __amdgpu_buffer_rsrc_t yrs = rsrc_of(Y + h * BHD, (uint32_t)(NY - 1) * (uint32_t)ldy * 2u + (uint32_t)BHD * 2u);
-  const __amdgpu_buffer_rsrc_t y2rs = rsrc_of(Y2 + h * BHD, (uint32_t)(NY - 1) * (uint32_t)ldy2 * 2u + (uint32_t)BHD * 2u);
+  const __amdgpu_buffer_rsrc_t yrs = rsrc_of(Y + hc * BHD, (uint32_t)(NY - 1) * (uint32_t)ldy * 2u + (uint32_t)BHD * 2u);
+  const __amdgpu_buffer_rsrc_t y2rs = rsrc_of(Y2 + hc * BHD, (uint32_t)(NY - 1) * (uint32_t)ldy2 * 2u + (uint32_t)BHD * 2u);
   const __amdgpu_buffer_rsrc_t lrs = rsrc_of(lse2 + (size_t)h * R, (uint32_t)NY * 4u);     // MODE 1-3: NY == R (queries)
   const __amdgpu_buffer_rsrc_t drs = rsrc_of(delta + (size_t)h * R, (uint32_t)NY * 4u);
   int yoff[4], y2off[4];
@@ -341,7 +354,7 @@ __global__ __launch_bounds__(256, (MODE == 3 ? 1 : 2)) void attn_bwd_kernel(cons
   // ---- epilogue: Out[x][h*128 + 32db + 8g + 4hh + 0..3] = A^T * out_scale
   const int x = x0 + r;
   if (x < NX) {
-    uint16_t* op = Out + (size_t)x * ldo + h * BHD + 4 * hh;
+    uint16_t* op = Out + (size_t)x * ldo + hc * BHD + 4 * hh;
 #pragma unroll
     for (int db = 0; db < 4; ++db)
 #pragma unroll
@@ -349,7 +362,7 @@ __global__ __launch_bounds__(256, (MODE == 3 ? 1 : 2)) void attn_bwd_kernel(cons
         *(u32x2*)(op + 32 * db + 8 * g) = pack4<T>(acc[db][4 * g] * out_scale, acc[db][4 * g + 1] * out_scale,
                                                    acc[db][4 * g + 2] * out_scale, acc[db][4 * g + 3] * out_scale);
     if (MODE == 3) {
-      uint16_t* op2 = Out2 + (size_t)x * ldo2 + h * BHD + 4 * hh;
+      uint16_t* op2 = Out2 + (size_t)x * ldo2 + hc * BHD + 4 * hh;
 #pragma unroll
       for (int db = 0; db < 4; ++db)
 #pragma unroll
@@ -360,14 +373,16 @@ __global__ __launch_bounds__(256, (MODE == 3 ? 1 : 2)) void attn_bwd_kernel(cons
   }
 }
 
-// delta[h][q] = sum_d dO[q, h*128+d] * O[q, h*128+d]; one wave per query row, 8 lanes per head.
+// delta[vb*H + h][q] = sum_d dO[vb*R + q, h*128+d] * O[vb*R + q, h*128+d]; one wave per query row, 8 lanes per head.  Row batch:
+// nb videos of R stacked rows and H heads each (delta is [nb*H, R]).
 template <typename T>
 __global__ __launch_bounds__(256) void attn_delta_kernel(const uint16_t* __restrict__ O, int ldo,
                                                          const uint16_t* __restrict__ dO, int lddo,
-                                                         float* __restrict__ delta, int R, int H) {
+                                                         float* __restrict__ delta, int R, int H, int nb) {
   const int lane = threadIdx.x & 63;
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (q >= R) return;
+  if (q >= nb * R) return;
+  const int vb = q / R;
   for (int c0 = 0; c0 < H * BHD; c0 += 1024) {
     const int col = c0 + lane * 16;
     float s = 0.f;
@@ -383,22 +398,23 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const uint16_t* __restr
     s += __shfl_xor(s, 1);
     s += __shfl_xor(s, 2);
     s += __shfl_xor(s, 4);
-    if ((lane & 7) == 0 && col < H * BHD) delta[(size_t)(col / BHD) * R + q] = s;
+    if ((lane & 7) == 0 && col < H * BHD) delta[(size_t)(vb * H + col / BHD) * R + (q - vb * R)] = s;
   }
 }
 
 template <typename T, int MODE>
 void launch_mode(dim3 grid, hipStream_t s, const void* X, int ldx, const void* X2, int ldx2, const void* Y, int ldy,
                  const void* Y2, int ldy2, const float* lse2, const float* delta, void* out, int ldo, int NX, int NY,
-                 int R, int H, float c, float out_scale, void* out2 = nullptr, int ldo2 = 0) {
+                 int R, const mavlm_attn_bwd_args& a, float c, float out_scale, void* out2 = nullptr, int ldo2 = 0) {
   hipLaunchKernelGGL((attn_bwd_kernel<T, MODE>), grid, dim3(256), BWD_LDS, s, (const uint16_t*)X, ldx, (const uint16_t*)X2,
                      ldx2, (const uint16_t*)Y, ldy, (const uint16_t*)Y2, ldy2, lse2, delta, (uint16_t*)out, ldo, NX, NY,
-                     R, H, c, out_scale, (uint16_t*)out2, ldo2);
+                     R, a.H, c, out_scale, (uint16_t*)out2, ldo2, a.H / a.nb, a.kv_bstride, a.dkv_bstride);
 }
 
 template <typename T>
 hipError_t launch_all(const mavlm_attn_bwd_args& a, hipStream_t s) {
-  // streamed operands are addressed through 32-bit buffer offsets (one tile past the end included)
+  // streamed operands are addressed through 32-bit buffer offsets (one tile past the end included); a row batch moves the
+  // descriptors to the video, so the limit is one video's
   const double lim = 2147483648.0;
   if (((double)a.S + 64) * a.ldk * 2.0 >= lim || ((double)a.S + 64) * a.ldv * 2.0 >= lim ||
       ((double)a.R + 64) * a.ldq * 2.0 >= lim || ((double)a.R + 64) * a.lddo * 2.0 >= lim)
@@ -412,23 +428,24 @@ hipError_t launch_all(const mavlm_attn_bwd_args& a, hipStream_t s) {
     if (e == hipSuccess) e = once[3].dyn_lds((const void*)attn_bwd_kernel<T, 3>, BWD_LDS);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(attn_delta_kernel<T>, dim3((a.R + 3) / 4), dim3(256), 0, s, (const uint16_t*)a.O, a.ldo,
-                     (const uint16_t*)a.dO, a.lddo, a.delta, a.R, a.H);
+  if (a.nb < 1 || a.H % a.nb) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(attn_delta_kernel<T>, dim3((a.nb * a.R + 3) / 4), dim3(256), 0, s, (const uint16_t*)a.O, a.ldo,
+                     (const uint16_t*)a.dO, a.lddo, a.delta, a.R, a.H / a.nb, a.nb);
   const dim3 gq(((a.R + 127) / 128) * a.H), gk(((a.S + 127) / 128) * a.H);
   if (a.dQ != nullptr)
     launch_mode<T, 0>(gq, s, a.Q, a.ldq, a.dO, a.lddo, a.K, a.ldk, a.V, a.ldv, a.lse2, a.delta, a.dQ, a.lddq, a.R, a.S,
-                      a.R, a.H, c, a.scale);
+                      a.R, a, c, a.scale);
   if (a.dK != nullptr && a.dV != nullptr && g_mavlm_attn_bwd_fused) {
     launch_mode<T, 3>(gk, s, a.K, a.ldk, a.V, a.ldv, a.Q, a.ldq, a.dO, a.lddo, a.lse2, a.delta, a.dK, a.lddk, a.S, a.R,
-                      a.R, a.H, c, a.scale, a.dV, a.lddv);
+                      a.R, a, c, a.scale, a.dV, a.lddv);
     return hipGetLastError();
   }
   if (a.dK != nullptr)
     launch_mode<T, 1>(gk, s, a.K, a.ldk, a.V, a.ldv, a.Q, a.ldq, a.dO, a.lddo, a.lse2, a.delta, a.dK, a.lddk, a.S, a.R,
-                      a.R, a.H, c, a.scale);
+                      a.R, a, c, a.scale);
   if (a.dV != nullptr)
     launch_mode<T, 2>(gk, s, a.K, a.ldk, nullptr, 0, a.Q, a.ldq, a.dO, a.lddo, a.lse2, a.delta, a.dV, a.lddv, a.S, a.R,
-                      a.R, a.H, c, 1.0f);
+                      a.R, a, c, 1.0f);
   return hipGetLastError();
 }
 

@@ -65,7 +65,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_hd_kernel(const uint16_t* __r
                                                              const uint16_t* __restrict__ Y2, int ldy2,
                                                              const float* __restrict__ lse2, const float* __restrict__ delta,
                                                              uint16_t* __restrict__ Out, int ldo, int NX, int NY, int R, int H,
-                                                             float c, float out_scale, uint16_t* __restrict__ Out2, int ldo2) {
+                                                             float c, float out_scale, uint16_t* __restrict__ Out2, int ldo2,
+                                                             int Hv, long long kvb, long long okvb) {
   constexpr int NSUB = (HD + 127) / 128;
   constexpr int SUB = WKT * 256;                            // 8 KiB: [32 rows][256 B]
   constexpr int TILE = NSUB * SUB;                          // 32 KiB
@@ -91,6 +92,16 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_hd_kernel(const uint16_t* __r
   const int x0 = (blockIdx.x / H) * (32 * (4 / SL)) + grp * 32;
   const int r = lane & 31, hh = lane >> 5;
   const int nt = (NY + WKT - 1) / WKT;
+  // row batch (as attn_bwd_kernel): head h of the launch is head hc of video vb; every operand moves to that video's rows, so
+  // that row indices, descriptor ends and 32-bit offsets stay those of ONE video.  (A single video: vb = 0, hc = h.)
+  const int vb = h / Hv, hc = h - vb * Hv;
+  if (MODE == 0) {
+    X += (size_t)vb * NX * ldx; X2 += (size_t)vb * NX * ldx2; Y += vb * kvb; Y2 += vb * kvb; Out += (size_t)vb * NX * ldo;
+  } else {
+    X += vb * kvb; Y += (size_t)vb * NY * ldy; Y2 += (size_t)vb * NY * ldy2; Out += vb * okvb;
+    if (MODE != 2) X2 += vb * kvb;
+    if (MODE == 3) Out2 += vb * okvb;
+  }
 
   // ---- stationary fragments (B operand) of this wave's first-phase product: lane holds X[x0 + r][h*HD + 16 ks + 8 hh + 0..7]
   // (role 1: X2)
@@ -99,7 +110,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_hd_kernel(const uint16_t* __r
   xrow = xrow < NX ? xrow : NX - 1;
   {
     const uint16_t* xp = (TWO && slab == 1) ? X2 + (size_t)xrow * ldx2 : X + (size_t)xrow * ldx;
-    xp += h * HD + 8 * hh;
+    xp += hc * HD + 8 * hh;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) xf[ks] = *(const typename T::vec8*)(xp + 16 * ks);
   }
@@ -121,8 +132,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_hd_kernel(const uint16_t* __r
     return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes),
                                              0x00020000);
   };
-  const __amdgpu_buffer_rsrc_t yrs = rsrc_of(Y + h * HD, (uint32_t)(NY - 1) * (uint32_t)ldy * 2u + (uint32_t)HD * 2u);
-  const __amdgpu_buffer_rsrc_t y2rs = rsrc_of(Y2 + h * HD, (uint32_t)(NY - 1) * (uint32_t)ldy2 * 2u + (uint32_t)HD * 2u);
+  const __amdgpu_buffer_rsrc_t yrs = rsrc_of(Y + hc * HD, (uint32_t)(NY - 1) * (uint32_t)ldy * 2u + (uint32_t)HD * 2u);
+  const __amdgpu_buffer_rsrc_t y2rs = rsrc_of(Y2 + hc * HD, (uint32_t)(NY - 1) * (uint32_t)ldy2 * 2u + (uint32_t)HD * 2u);
   const __amdgpu_buffer_rsrc_t lrs = rsrc_of(lse2 + (size_t)h * R, (uint32_t)NY * 4u);     // MODE 1-3: NY == R (queries)
   const __amdgpu_buffer_rsrc_t drs = rsrc_of(delta + (size_t)h * R, (uint32_t)NY * 4u);
   const int drow = 4 * wave + (lane >> 4);
@@ -356,7 +367,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_hd_kernel(const uint16_t* __r
   // ---- epilogue: Out[x][h*HD + 32 (SL db + slab) + 8 g + 4 hh + 0..3] = A^T * out_scale
   const int x = x0 + r;
   if (x < NX) {
-    uint16_t* op = Out + (size_t)x * ldo + h * HD + 32 * slab + 4 * hh;
+    uint16_t* op = Out + (size_t)x * ldo + hc * HD + 32 * slab + 4 * hh;
 #pragma unroll
     for (int db = 0; db < DBS; ++db)
 #pragma unroll
@@ -364,7 +375,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_hd_kernel(const uint16_t* __r
         *(u32x2*)(op + 32 * SL * db + 8 * g) = pack4<T>(acc[db][4 * g] * out_scale, acc[db][4 * g + 1] * out_scale,
                                                         acc[db][4 * g + 2] * out_scale, acc[db][4 * g + 3] * out_scale);
     if constexpr (DKV) {
-      uint16_t* op2 = Out2 + (size_t)x * ldo2 + h * HD + 32 * slab + 4 * hh;
+      uint16_t* op2 = Out2 + (size_t)x * ldo2 + hc * HD + 32 * slab + 4 * hh;
 #pragma unroll
       for (int db = 0; db < DBS; ++db)
 #pragma unroll
@@ -380,15 +391,15 @@ constexpr int bwd_hd_lds(int hd) { return 4 * ((hd + 127) / 128) * WKT * 256 + 1
 template <typename T, int MODE, int HD>
 void launch_mode_hd(dim3 grid, hipStream_t s, const void* X, int ldx, const void* X2, int ldx2, const void* Y, int ldy,
                     const void* Y2, int ldy2, const float* lse2, const float* delta, void* out, int ldo, int NX, int NY, int R,
-                    int H, float c, float out_scale, void* out2 = nullptr, int ldo2 = 0) {
+                    const mavlm_attn_bwd_args& a, float c, float out_scale, void* out2 = nullptr, int ldo2 = 0) {
   hipLaunchKernelGGL((attn_bwd_hd_kernel<T, MODE, HD>), grid, dim3(256), bwd_hd_lds(HD), s, (const uint16_t*)X, ldx,
                      (const uint16_t*)X2, ldx2, (const uint16_t*)Y, ldy, (const uint16_t*)Y2, ldy2, lse2, delta, (uint16_t*)out,
-                     ldo, NX, NY, R, H, c, out_scale, (uint16_t*)out2, ldo2);
+                     ldo, NX, NY, R, a.H, c, out_scale, (uint16_t*)out2, ldo2, a.H / a.nb, a.kv_bstride, a.dkv_bstride);
 }
 
 template <typename T, int HD>
 hipError_t launch_all_hd(const mavlm_attn_bwd_args& a, int dtype, hipStream_t s) {
-  // streamed operands are addressed through 32-bit buffer offsets (one tile past the end included)
+  // streamed operands are addressed through 32-bit buffer offsets (one tile past the end included; per video in a row batch)
   const double lim = 2147483648.0;
   if (((double)a.S + 64) * a.ldk * 2.0 >= lim || ((double)a.S + 64) * a.ldv * 2.0 >= lim ||
       ((double)a.R + 64) * a.ldq * 2.0 >= lim || ((double)a.R + 64) * a.lddo * 2.0 >= lim)
@@ -402,25 +413,29 @@ hipError_t launch_all_hd(const mavlm_attn_bwd_args& a, int dtype, hipStream_t s)
     if (e == hipSuccess) e = once[3].dyn_lds((const void*)attn_bwd_hd_kernel<T, 3, HD>, bwd_hd_lds(HD));
     if (e != hipSuccess) return e;
   }
-  {
-    hipError_t e = mavlm_launch_rowdot(a.dO, a.lddo, a.O, a.ldo, a.delta, a.R, a.H, HD, dtype, s);
+  if (a.nb < 1 || a.H % a.nb) return hipErrorInvalidValue;
+  for (int b = 0; b < a.nb; ++b) {        // delta [nb*Hv, R]: one pass per video over its R stacked rows
+    const int Hv = a.H / a.nb;
+    hipError_t e = mavlm_launch_rowdot((const uint16_t*)a.dO + (size_t)b * a.R * a.lddo, a.lddo,
+                                       (const uint16_t*)a.O + (size_t)b * a.R * a.ldo, a.ldo, a.delta + (size_t)b * Hv * a.R, a.R, Hv,
+                                       HD, dtype, s);
     if (e != hipSuccess) return e;
   }
   const dim3 gq(((a.R + 63) / 64) * a.H), gk(((a.S + 63) / 64) * a.H), gv(((a.S + 127) / 128) * a.H);
   if (a.dQ != nullptr)
     launch_mode_hd<T, 0, HD>(gq, s, a.Q, a.ldq, a.dO, a.lddo, a.K, a.ldk, a.V, a.ldv, a.lse2, a.delta, a.dQ, a.lddq, a.R, a.S,
-                             a.R, a.H, c, a.scale);
+                             a.R, a, c, a.scale);
   if (a.dK != nullptr && a.dV != nullptr) {
     launch_mode_hd<T, 3, HD>(gk, s, a.K, a.ldk, a.V, a.ldv, a.Q, a.ldq, a.dO, a.lddo, a.lse2, a.delta, a.dK, a.lddk, a.S, a.R,
-                             a.R, a.H, c, a.scale, a.dV, a.lddv);
+                             a.R, a, c, a.scale, a.dV, a.lddv);
     return hipGetLastError();
   }
   if (a.dK != nullptr)
     launch_mode_hd<T, 1, HD>(gk, s, a.K, a.ldk, a.V, a.ldv, a.Q, a.ldq, a.dO, a.lddo, a.lse2, a.delta, a.dK, a.lddk, a.S, a.R,
-                             a.R, a.H, c, a.scale);
+                             a.R, a, c, a.scale);
   if (a.dV != nullptr)
     launch_mode_hd<T, 2, HD>(gv, s, a.K, a.ldk, nullptr, 0, a.Q, a.ldq, a.dO, a.lddo, a.lse2, a.delta, a.dV, a.lddv, a.S, a.R,
-                             a.R, a.H, c, 1.0f);
+                             a.R, a, c, 1.0f);
   return hipGetLastError();
 }
 

@@ -1153,6 +1153,40 @@ int mavlm_attention_hd_ws(const void* Q, int32_t ldq, const void* K, int32_t ldk
   return (int)mavlm_launch_attention_hd(a, head_dim, dtype, (hipStream_t)stream);
 }
 
+// ---- row-batched operators (the training path of BatchedProjector): nb videos per launch, as attn_block runs them
+static int batch_args_bad(int32_t H, int32_t nb) { return nb < 1 || nb > MAVLM_MAX_BATCH || H <= 0 || H % nb != 0; }
+
+int64_t mavlm_attention_batch_ws_floats(int32_t R, int32_t S, int32_t H, int32_t nb, int32_t head_dim) {
+  if (R <= 0 || S <= 0 || head_dim <= 0 || batch_args_bad(H, nb)) return 0;
+  // attn_block's rule: the stream-K plan over all H (video, head) pairs where it applies; the split-KV form of the small
+  // grids for a single video only
+  if (head_dim == 448)
+    return (nb == 1 || mavlm_attention_hd_streamk(R, S, H, head_dim, nullptr) > 0) ? (int64_t)mavlm_attention_hd_split_ws_floats(R, S, H, head_dim) : 0;
+  if (head_dim > 128) return 0;
+  return (nb == 1 || mavlm_attention_streamk_wgs(R, S, H) > 0) ? (int64_t)mavlm_attention_split_ws_floats(R, S, H) : 0;
+}
+
+int mavlm_attention_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, void* O,
+                          int32_t ldo, float* lse2, int32_t R, int32_t S, int32_t H, float scale, float* ws_,
+                          int64_t ws_floats, int32_t nb, int64_t kv_bstride, int32_t head_dim, int32_t dtype, void* stream) {
+  if (!Q || !K || !V || !O || R <= 0 || S <= 0 || batch_args_bad(H, nb) || kv_bstride < 0) return MAVLM_E_ARG;
+  if (head_dim != 448 && (head_dim <= 0 || head_dim > 128)) return MAVLM_E_SHAPE;
+  const int hw = head_dim == 448 ? 448 : 128;                  // columns a head occupies (narrow heads: zero-padded to 128)
+  const int Hv = H / nb;
+  if ((ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 3) || ldq < Hv * hw || ldk < Hv * hw || ldv < Hv * hw || ldo < Hv * hw ||
+      (kv_bstride & 7))
+    return MAVLM_E_ARG;
+  const int64_t need = mavlm_attention_batch_ws_floats(R, S, H, nb, head_dim);
+  if (need > 0 && (!ws_ || ws_floats < need)) return MAVLM_E_ARG;        // the plan is part of the result
+  mavlm_attn_args a;
+  a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = O; a.ldo = ldo; a.lse2 = lse2;
+  a.R = R; a.S = S; a.H = H; a.scale = scale; a.nb = nb; a.kv_bstride = kv_bstride;
+  a.split_ws = need > 0 ? ws_ : nullptr;
+  hipError_t e = hw == 448 ? mavlm_launch_attention_hd(a, head_dim, dtype, (hipStream_t)stream)
+                           : mavlm_launch_attention(a, dtype, (hipStream_t)stream);
+  return e == hipErrorInvalidValue ? MAVLM_E_ARG : (int)e;
+}
+
 int mavlm_attention_colsum_hd(const void* Q, int32_t ldq, const void* K, int32_t ldk, const float* lse2, float* part,
                               int32_t R, int32_t S, int32_t H, int32_t head_dim, float scale, int32_t dtype, void* stream) {
   if (!Q || !K || !lse2 || !part || R <= 0 || S <= 0 || H <= 0 || (ldq & 7) || (ldk & 7)) return MAVLM_E_ARG;
@@ -1281,6 +1315,52 @@ int mavlm_attention_bwd_hd(const void* Q, int32_t ldq, const void* K, int32_t ld
                         (hipStream_t)stream);
   hipError_t e = mavlm_launch_attention_bwd_hd(a, head_dim, dtype, (hipStream_t)stream);
   return e == hipErrorInvalidValue ? MAVLM_E_ARG : (int)e;
+}
+
+// row-batched backward: arguments checked before anything is enqueued (hw = columns of a head: 128 or 448)
+static int attention_bwd_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, const void* O,
+                               int32_t ldo, const void* dO, int32_t lddo, const float* lse2, float* delta, void* dQ, int32_t lddq,
+                               void* dK, int32_t lddk, void* dV, int32_t lddv, int32_t R, int32_t S, int32_t H, int hw, float scale,
+                               int32_t nb, int64_t kv_bstride, int64_t dkv_bstride, int32_t dtype, void* stream) {
+  if (!Q || !K || !V || !O || !dO || !lse2 || !delta || R <= 0 || S <= 0 || batch_args_bad(H, nb)) return MAVLM_E_ARG;
+  if (hw != 128 && hw != 448) return MAVLM_E_SHAPE;
+  if ((ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) || (lddo & 7) || (lddq & 3) || (lddk & 3) || (lddv & 3))
+    return MAVLM_E_ARG;
+  const int w = (H / nb) * hw;
+  if (ldq < w || ldk < w || ldv < w || ldo < w || lddo < w || (dQ && lddq < w) || (dK && lddk < w) || (dV && lddv < w))
+    return MAVLM_E_ARG;
+  if (kv_bstride < 0 || dkv_bstride < 0 || (kv_bstride & 7) || (dkv_bstride & 3)) return MAVLM_E_ARG;
+  if (nb > 1 && (kv_bstride == 0 || ((dK || dV) && dkv_bstride == 0))) return MAVLM_E_ARG;     // (videos on top of each other)
+  if (((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O | (uintptr_t)dO) & 15) return MAVLM_E_ARG;
+  if (((uintptr_t)dQ | (uintptr_t)dK | (uintptr_t)dV) & 7) return MAVLM_E_ARG;
+  mavlm_attn_bwd_args a;
+  a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = O; a.ldo = ldo; a.dO = dO; a.lddo = lddo;
+  a.lse2 = lse2; a.delta = delta; a.dQ = dQ; a.lddq = lddq; a.dK = dK; a.lddk = lddk; a.dV = dV; a.lddv = lddv;
+  a.R = R; a.S = S; a.H = H; a.scale = scale; a.nb = nb; a.kv_bstride = kv_bstride; a.dkv_bstride = dkv_bstride;
+  const double units = (dQ ? 3.0 : 0.0) + (dK ? 3.0 : 0.0) + (dV ? 2.0 : 0.0);
+  mavlm_prof_scope prof(MAVLM_K_ATTN_BWD, units * 2.0 * R * (double)S * H * hw, 2.0 * hw * H * (4.0 * R + 4.0 * S),
+                        (hipStream_t)stream);
+  hipError_t e = hw == 448 ? mavlm_launch_attention_bwd_hd(a, 448, dtype, (hipStream_t)stream)
+                           : mavlm_launch_attention_bwd(a, dtype, (hipStream_t)stream);
+  return e == hipErrorInvalidValue ? MAVLM_E_ARG : (int)e;
+}
+
+int mavlm_attention_bwd_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, const void* O,
+                              int32_t ldo, const void* dO, int32_t lddo, const float* lse2, float* delta, void* dQ,
+                              int32_t lddq, void* dK, int32_t lddk, void* dV, int32_t lddv, int32_t R, int32_t S, int32_t H,
+                              float scale, int32_t nb, int64_t kv_bstride, int64_t dkv_bstride, int32_t dtype, void* stream) {
+  return attention_bwd_batch(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse2, delta, dQ, lddq, dK, lddk, dV, lddv, R, S, H, 128,
+                             scale, nb, kv_bstride, dkv_bstride, dtype, stream);
+}
+
+int mavlm_attention_bwd_hd_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv,
+                                 const void* O, int32_t ldo, const void* dO, int32_t lddo, const float* lse2, float* delta,
+                                 void* dQ, int32_t lddq, void* dK, int32_t lddk, void* dV, int32_t lddv, int32_t R, int32_t S,
+                                 int32_t H, int32_t head_dim, float scale, int32_t nb, int64_t kv_bstride, int64_t dkv_bstride,
+                                 int32_t dtype, void* stream) {
+  if (head_dim != 448 && Q && K && V && O && dO && lse2 && delta && R > 0 && S > 0 && !batch_args_bad(H, nb)) return MAVLM_E_SHAPE;
+  return attention_bwd_batch(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse2, delta, dQ, lddq, dK, lddk, dV, lddv, R, S, H,
+                             head_dim, scale, nb, kv_bstride, dkv_bstride, dtype, stream);
 }
 
 int mavlm_linear_splitk(const void* A, int32_t lda, const void* W, int32_t ldw, void* C, int32_t M, int32_t N, int32_t K,

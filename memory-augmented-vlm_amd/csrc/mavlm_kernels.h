@@ -155,6 +155,12 @@ struct mavlm_attn_bwd_args {
   void* dV; int lddv;
   int R, S, H;
   float scale;
+  // row batch, with the forward's meaning (mavlm_attn_args): H counts the heads of ALL videos (nb x heads per video); Q / O /
+  // dO / dQ hold the nb x R rows of the videos one after the other; lse2 / delta are [H, R] with h = b * (H / nb) + head; video
+  // b's keys start b * kv_bstride elements into K and V, its dK / dV b * dkv_bstride elements into theirs.  Every output row
+  // keeps one owner: a batched launch gives the bits of nb single launches.  nb = 1: a single video.
+  int nb = 1;
+  long long kv_bstride = 0, dkv_bstride = 0;
 };
 hipError_t mavlm_launch_attention_bwd(const mavlm_attn_bwd_args& a, int dtype, hipStream_t s);
 // the same for head_dim 448 (attention_bwd_hd.hip); O / dO / dQ / dK / dV are [rows, H*448]

@@ -334,6 +334,60 @@ def video_memory_tokens_batched(model, bp: BatchedProjector, images, frame_idx_c
     return out, info
 
 
+def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame_idx_cpu: torch.Tensor,
+                                      memory_prompt_embeds: torch.Tensor, frame_prompt_embeds: torch.Tensor,
+                                      image_newline: Optional[torch.Tensor], with_frames: bool = True, chunk: int = 32,
+                                      fine_frames: int = 32, layout: str = "one_token"):
+    """`video_memory_tokens_batched` under autograd: B videos of the same length stepped together by
+    `BatchedProjector.step_train`, then the tail of `_video_memory_tokens_autograd` over all videos - the fuser MLP runs ONCE
+    over the B * n * M * 196 stacked memory rows (HIP autograd Functions); the token-type adds, the layout and the concatenation
+    are torch ops, so autograd routes the gradients of token_type_embedding, the prompt embeddings and image_newline as in the
+    reference.  Returns (tokens [B, rows, D] with grad - the bits of `video_memory_tokens_batched` -, info)."""
+    from .. import _autograd as ag
+    layout_period(layout, images[0].shape[1])
+    B = bp.batch
+    if len(images) != B:
+        raise capi.MavlmError(f"video_memory_tokens_batched_train: {B} videos expected")
+    T, P, D = images[0].shape
+    for im in images:
+        if not im.is_cuda or tuple(im.shape) != (T, P, D) or im.dtype != images[0].dtype:
+            raise capi.MavlmError("video_memory_tokens_batched_train: GPU frame tokens of one shape / dtype expected")
+    pe: TemporalPositionalEncoding = model.positional_encoding
+    rm: TransformerProjector = model.recurrent_memory_transformer
+    dev, dt = images[0].device, images[0].dtype
+    pe.check_indices(frame_idx_cpu)
+    idx_dev = _device_indices(frame_idx_cpu, dev)
+    xs = [pe(im, idx_dev, indices_checked=True) for im in images]                           # :510-511
+    fine_cpu = fine_frame_indices(T, fine_frames)                                          # :513-522
+    bounds = uniform_segment_variant(T, chunk)                                             # :528
+    bp.reset()                                                                             # :532
+    for i in range(len(bounds) - 1):                                                       # :534-537
+        bp.step_train([x[bounds[i]:bounds[i + 1]] for x in xs])
+    n = len(bp._tcache)
+    R = rm.num_memory_tokens * P
+    temb = model.token_type_embedding.weight
+    mem = torch.cat(bp._tcache, dim=0)                                                     # [n * B * R, D], oldest first (:545)
+    fused = ag.fuser_mlp(model.memory_fuser, mem, temb[0], fused_gelu=True).view(n, B, R, D)       # :546-553
+    _require_newline(image_newline, layout)
+    nl = None if layout == "no_token" else image_newline.to(device=dev, dtype=dt).reshape(1, D)
+    mp, fp = memory_prompt_embeds.to(dt), frame_prompt_embeds.to(dt)
+    fine_dev = _device_indices(fine_cpu, dev)
+    toks = []
+    mem_rows = 0
+    for b in range(B):
+        mem_block = _lay_out_block(fused[:, b].reshape(n * R, D), nl, layout, P)           # :567-634
+        mem_rows = mem_block.shape[0]
+        parts = [mp, mem_block]
+        if with_frames:
+            fine = xs[b][fine_dev] + temb[1].to(dt)                                        # :513-524,554
+            parts += [fp, _lay_out_block(fine.reshape(-1, D), nl, layout, P)]
+        toks.append(torch.cat(parts, dim=0))
+    info = {"num_memories": n, "pe_frames": xs, "fine_idx": fine_cpu,
+            "memory_rows": (mp.shape[0], mp.shape[0] + (mem_rows if layout_period(layout, P) else n * R)),
+            "frame_scores": bp.frame_scores}
+    return torch.stack(toks), info
+
+
 def _tail_wants_grad(model, *tensors) -> bool:
     """Can anything AFTER the recurrent steps receive a gradient?  (`memory_fuser`, `token_type_embedding`, and the
     tensors the caller hands in: prompt embeddings of a trainable `embed_tokens`, `image_newline`.)"""

@@ -701,8 +701,16 @@ class BatchedProjector:
         bp.reset()
         for chunk in chunks:  bp.step([x_b[lo:hi] for x_b in videos])      # x_b: [T, P, D] PE-added frames of video b
         bp.memory_cache(b) -> list of [M, P, D] ring views of video b;  bp.frame_scores -> list of [B, F] per chunk
-    Inference only (no autograd path).  Same kernels and rounding points as the single-video engine; the attention's fp32
-    summation order follows the schedule of the stacked grid."""
+    Same kernels and rounding points as the single-video engine; the attention's fp32 summation order follows the schedule
+    of the stacked grid.
+
+    `step` is the inference step (no_grad: one fused launch sequence, `mavlm_step_batch`).  `step_train` is the same step
+    under autograd - the training path of `TransformerProjector._forward_autograd` over the stacked rows of the B videos, in
+    the launch order of `mavlm_step_batch`: every GEMM, LayerNorm and their backward run ONCE over [B*R, D] operands (one dW
+    contraction over all videos' rows: fp32 accumulation, one rounding), forward and backward attention serve the B*heads
+    (video, head) pairs in one launch each.  Its activations are bit-identical to `step`'s; `memory_cache(b)` then returns
+    graph-carrying [M, P, D] tensors (BPTT through the un-detached FIFO, as the reference) and `frame_scores` the detached
+    [B, F] scores.  One video batch runs in one mode: `reset()` between `step` and `step_train`."""
 
     def __init__(self, proj: TransformerProjector, batch: int, fused_ln_never: bool = False):
         self.fused_ln_never = bool(fused_ln_never)
@@ -716,6 +724,9 @@ class BatchedProjector:
         self.record_attention_maps = False    # True: every step appends an AttentionMaps with a leading video axis
         self.attention_maps: List[AttentionMaps] = []
         self._n = 0
+        self._mode = None                     # "engine" (step) / "autograd" (step_train) once a video batch has started
+        self._tcache = []                     # training path: the cached memories, stacked [B*R, D] graph tensors, oldest first
+        self._tevo = []                       # ... and their evolution K/V projections ([B, R, Dp] views), one pair per entry
 
     def engine(self, device, dtype, frames=None) -> _Engine:
         proj = self.proj
@@ -738,6 +749,8 @@ class BatchedProjector:
         self.frame_scores = []
         self.attention_maps = []
         self._n = 0
+        self._mode = None
+        self._tcache, self._tevo = [], []
         if self._engine is not None:
             capi.check(capi.lib().mavlm_reset(self._engine.ctx), "mavlm_reset")
             if self.proj._weights_maybe_stale(self._packed_epoch):
@@ -755,6 +768,10 @@ class BatchedProjector:
                 raise capi.MavlmError("BatchedProjector.step: contiguous GPU chunks of one shape / dtype expected")
         if P != self.proj.patch_size or D != self.proj.hidden_size:
             raise capi.MavlmError(f"expected [F,{self.proj.patch_size},{self.proj.hidden_size}] chunks")
+        if self._mode == "autograd":
+            raise capi.MavlmError("BatchedProjector.step: this video batch holds autograd tensors of `step_train`: `reset()` "
+                                  "before running the inference step")
+        self._mode = "engine"
         eng = self.engine(segs[0].device, segs[0].dtype, F)
         ptrs = (capi.vp * self.batch)(*[t.data_ptr() for t in segs])
         scores = torch.empty((self.batch, F), device=segs[0].device, dtype=segs[0].dtype) if self.compute_frame_scores else None
@@ -772,8 +789,103 @@ class BatchedProjector:
             self.frame_scores.append(scores)
         return scores
 
+    def step_train(self, segs):
+        """One chunk of every video under autograd (see the class docstring): segs = B tensors [F, P, D] of one shape.  Mirrors
+        `TransformerProjector._forward_autograd` over the stacked rows, in the launch order of `mavlm_step_batch`.  Returns the
+        detached [B, F] frame scores (None with `compute_frame_scores = False`)."""
+        from ... import _autograd as ag
+        proj, B = self.proj, self.batch
+        if self.record_attention_maps:
+            raise capi.MavlmError("record_attention_maps is not supported on the autograd (training) path: attention maps are "
+                                  "recorded by inference steps only")
+        if len(segs) != B:
+            raise capi.MavlmError(f"BatchedProjector.step_train: {B} chunks expected")
+        if any(t.dim() != 3 for t in segs):
+            raise capi.MavlmError("BatchedProjector.step_train: [F, P, D] chunks expected")
+        F, P, D = segs[0].shape
+        for t in segs:
+            if not t.is_cuda or tuple(t.shape) != (F, P, D) or t.dtype != segs[0].dtype:
+                raise capi.MavlmError("BatchedProjector.step_train: GPU chunks of one shape / dtype expected")
+        if P != proj.patch_size or D != proj.hidden_size or F < 1:
+            raise capi.MavlmError(f"expected [F,{proj.patch_size},{proj.hidden_size}] chunks")
+        if self._mode == "engine":
+            raise capi.MavlmError("BatchedProjector.step_train: this video batch was started by the inference `step`: `reset()` "
+                                  "before running the training path")
+        self._mode = "autograd"
+        proj._train_state["epoch"] += 1          # an optimizer step may follow: packed copies are suspect afterwards
+        dt = segs[0].dtype
+        M = proj.num_memory_tokens
+        R = M * P
+        S = F * P
+        cap = int(getattr(proj.config, "cache_cap", 10))
+        evo = proj.memory_update_attention
+        if self._tcache:                                            # memory evolution (MemoryController.py:89-97, 125-127)
+            # each cached memory is projected once, when it is the newest: one packed GEMM over the stacked rows of all videos
+            while len(self._tevo) < len(self._tcache):
+                self._tevo.append(ag.project_kv([evo], self._tcache[len(self._tevo)], nb=B)[0])
+            # keys of a video in the slot order of the inference ring (memory g lives in slot g % cap): the attention sums in
+            # the same order after the FIFO has wrapped
+            first = self._n - len(self._tevo)
+            order = sorted(range(len(self._tevo)), key=lambda i: (first + i) % cap)
+            k = torch.cat([self._tevo[i][0] for i in order], dim=1)                    # [B, n*R, Dp]
+            v = torch.cat([self._tevo[i][1] for i in order], dim=1)
+            m, _ = ag.attention_block(evo, self._tcache[-1], k, v, nb=B)
+        else:
+            self._tevo = []
+            m = (proj.initial_memory + proj.memory_pos_embed).to(dt).reshape(R, D).repeat(B, 1)      # :123-124, every video
+        atts = [layer.memory_segment_fusion_attention for layer in proj.layers]
+        kvs = self._chunk_kv(ag, atts, segs, S, D)
+        stats = None
+        for li, layer in enumerate(proj.layers):                    # memory formation (:132-133)
+            last_layer = li == len(proj.layers) - 1
+            a, stats = ag.attention_block(atts[li], m, kvs[li][0], kvs[li][1], want_stats=last_layer and self.compute_frame_scores,
+                                          patches_per_frame=P, nb=B)
+            m = ag.mlp_block(layer, a)
+        self._tcache.append(m)                                      # :152
+        self._n += 1
+        if len(self._tcache) > cap:
+            drop = len(self._tcache) - cap
+            self._tcache = self._tcache[drop:]
+            self._tevo = self._tevo[drop:]
+        scores = None
+        if stats is not None:                                       # :135-139, 156 (detached statistics)
+            scores = self._train_frame_scores(stats, atts[-1], F, P, R, dt)
+            self.frame_scores.append(scores)
+        return scores
+
+    def _chunk_kv(self, ag, atts, segs, S, D):
+        """K/V of the chunk for all layers as [B, S, W] views: ONE GEMM over the stacked frames where that gives the bits of the
+        step's per-video GEMMs (row-independent kernels; only a split contraction - `mavlm_linear_ws_floats`, a function of
+        the row count - sums in another order), else one GEMM per video as the step runs them."""
+        B = self.batch
+        frames = [t.detach().reshape(S, D) for t in segs]           # frame features carry no gradient (llava_arch.py:302)
+        a0 = atts[0]
+        N = 2 * len(atts) * a0.num_attention_heads * ag.head_width(a0.attention_head_size)
+        lib = capi.lib()
+        if lib.mavlm_linear_ws_floats(S, N, D, capi.EPI_BIAS, N) == 0 and lib.mavlm_linear_ws_floats(B * S, N, D, capi.EPI_BIAS, N) == 0:
+            return ag.project_kv(atts, torch.cat(frames, dim=0), nb=B)
+        per = [ag.project_kv(atts, f) for f in frames]
+        return [(torch.stack([p[i][0] for p in per]), torch.stack([p[i][1] for p in per])) for i in range(len(atts))]
+
+    @torch.no_grad()
+    def _train_frame_scores(self, stats, att, F, P, R, dt):
+        """[B, F] frame scores of the last formation layer from its saved (q, k, lse2): the column-sum pass per video, exactly as
+        the single-video training path runs it (MemoryController.py:135-139)."""
+        q, k, lse = stats
+        H, hd = att.num_attention_heads, att.attention_head_size
+        out = []
+        for b in range(self.batch):
+            part = ops.attention_colsum(q[b * R:(b + 1) * R], k[b], lse[b * H:(b + 1) * H], H, head_dim=128 if hd <= 128 else hd,
+                                        scale=ops.attn_scale(hd))
+            out.append(part.sum(dim=0).view(F, P).mean(dim=1).to(dt))
+        return torch.stack(out)
+
     def memory_cache(self, b: int) -> List[torch.Tensor]:
-        """video b's FIFO, oldest first (ring views, as TransformerProjector.memory_cache)"""
+        """video b's FIFO, oldest first: ring views after `step` (as TransformerProjector.memory_cache), graph-carrying
+        [M, P, D] tensors after `step_train`"""
+        if self._mode == "autograd":
+            proj = self.proj
+            return [m.view(self.batch, proj.num_memory_tokens, proj.patch_size, proj.hidden_size)[b] for m in self._tcache]
         eng = self._engine
         cap = eng.c.cache_cap
         n = min(self._n, cap)

@@ -1,6 +1,9 @@
 """Diagnostic (not a test): one training step of the memory path at the bench shape - forward under autograd +
 backward, 64 frames, M=64, D=1024, bf16 - wall time and per-kernel-kind breakdown (HIP events).
-usage: python tools/bench_train.py [steps]"""
+usage: python tools/bench_train.py [steps]
+env: MEM_TOKENS, HIDDEN, BWD_FUSED; BATCH=B (default 1: the single-video path, the output below) or a list "1,2,4,8": the
+row-batched training step (BatchedProjector.step_train) of B distinct videos against the single-video step, the configurations
+interleaved round by round in this one process; ms per step and per video, then the kernel table of each."""
 import ctypes, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -32,6 +35,55 @@ def fwd_only():
         rm.memory_cache = []
         for i in range(2):
             rm(x[32 * i:32 * i + 32])
+
+BATCHES = [int(b) for b in os.environ.get("BATCH", "1").split(",")]
+
+def kernel_table(fn):
+    lib = capi.lib(); nk = len(capi.KERNEL_KINDS)
+    ms = (ctypes.c_double * nk)(); ln = (ctypes.c_int64 * nk)(); fl = (ctypes.c_double * nk)(); by = (ctypes.c_double * nk)()
+    lib.mavlm_prof_enable(1)
+    for _ in range(steps): fn()
+    torch.cuda.synchronize()
+    capi.check(lib.mavlm_prof_read(ms, ln, fl, by, nk), "prof"); lib.mavlm_prof_enable(0)
+    tot = sum(ms)
+    for i, name in enumerate(capi.KERNEL_KINDS):
+        if ln[i]:
+            print(f"{name:18s} launches/step {ln[i]/steps:6.1f}  ms/step {ms[i]/steps:8.3f}  ({100*ms[i]/tot:4.1f}%)  avg {ms[i]/ln[i]*1e3:8.1f} us"
+                  + (f"  {fl[i]/(ms[i]*1e-3)/1e12:7.1f} TF" if fl[i] else f"  {by[i]/(ms[i]*1e-3)/1e9:7.1f} GB/s"))
+    print(f"sum of HIP kernels {tot/steps:.2f} ms/step (torch glue kernels not included)")
+    return tot / steps
+
+if BATCHES != [1]:
+    from memory_augmented_vlm_amd.model.memory_module.MemoryController import BatchedProjector
+    xs = [x] + [(torch.randn(64, 196, HID, device="cuda") * 0.5).bfloat16() for _ in range(max(BATCHES) - 1)]   # distinct videos
+    def batched(B):
+        bp = BatchedProjector(rm, B)
+        def run():
+            rm.zero_grad(set_to_none=True)
+            bp.reset()
+            for i in range(2):
+                bp.step_train([v[32 * i:32 * i + 32] for v in xs[:B]])
+            loss = sum(cm.float().square().mean() for b in range(B) for cm in bp.memory_cache(b))
+            loss.backward()
+        return run
+    fns = {B: (step if B == 1 else batched(B)) for B in BATCHES}
+    for fn in fns.values():
+        for _ in range(2): fn()
+    times = {B: [] for B in BATCHES}
+    for _ in range(int(os.environ.get("ROUNDS", "3"))):
+        for B, fn in fns.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(steps): fn()
+            torch.cuda.synchronize(); times[B].append((time.perf_counter() - t0) / steps)
+    for B in BATCHES:
+        t = sorted(times[B])
+        print(f"BATCH={B}: train step (fwd+bwd) median {t[len(t)//2]*1e3:.2f} ms  min {t[0]*1e3:.2f}  max {t[-1]*1e3:.2f}   "
+              f"per video {t[len(t)//2]*1e3/B:.2f} ms   (M={M} hidden={HID}, rounds {['%.2f' % (v*1e3) for v in times[B]]})")
+    print(f"peak mem {torch.cuda.max_memory_allocated()/2**30:.2f} GiB")
+    for B in BATCHES:
+        print(f"---- kernel kinds, BATCH={B} (ms per step of {B} video(s))")
+        kernel_table(fns[B])
+    sys.exit(0)
 
 for _ in range(2): step()
 torch.cuda.synchronize(); t0 = time.perf_counter()
