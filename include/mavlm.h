@@ -234,6 +234,19 @@ int mavlm_fuse_emit_layout_batch(mavlm_ctx* ctx, const void* const* x_pe, const 
                                  const void* mem_prompt, int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt,
                                  const void* newline, int32_t with_frames, int32_t layout, void* out, int64_t rows_per_video,
                                  int64_t* rows, void* stream);
+/* mavlm_fuse_emit_layout_batch with one destination per video: video b's block is written at row dst_row[b] of `out`, a
+ * [out_rows, D] 16-bit buffer - the padded [B, L, D] inputs_embeds of a batch of samples, say, where prompts of different
+ * lengths and left padding put the blocks at rows that follow no constant stride.  dst_row = HOST array of B entries (B =
+ * mavlm_batch(ctx) <= 16), read during the call.  The launches are those of mavlm_fuse_emit_layout_batch (the fuser GEMM pair
+ * still runs once over the stacked rows) and the blocks are bit-identical to its blocks; the destinations reach the kernels by
+ * value - no allocation, no copy, no synchronisation.  Checked on the host before anything is enqueued, MAVLM_E_ARG otherwise:
+ * dst_row[b] >= 0, dst_row[b] + *rows <= out_rows, the B blocks pairwise disjoint, `out` 16-byte aligned.  MAVLM_E_STATE: a
+ * single-video context (mavlm_fuse_emit_layout writes wherever its `out` points).  Rows of `out` outside the blocks are not
+ * touched. */
+int mavlm_fuse_emit_layout_batch_to(mavlm_ctx* ctx, const void* const* x_pe, const int64_t* fine_idx, int32_t n_fine,
+                                    const void* mem_prompt, int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt,
+                                    const void* newline, int32_t with_frames, int32_t layout, void* out, int64_t out_rows,
+                                    const int64_t* dst_row, int64_t* rows, void* stream);
 /* Host only: rows of the token block of a video with n_memories cached memories and n_fine fine frames in a layout - the
  * sequence length the concat of llava_arch.py:722-731 ends up with after :567-634.  <0: MAVLM_E_ARG (bad config / counts /
  * layout), MAVLM_E_SHAPE (_GRID: patches is not a square). */

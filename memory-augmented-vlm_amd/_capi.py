@@ -76,6 +76,8 @@ SIGNATURES = {
                                   C.POINTER(C.c_int64), vp]),
     "mavlm_fuse_emit_layout_batch": (C.c_int, [vp, C.POINTER(vp), vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64,
                                                C.POINTER(C.c_int64), vp]),
+    "mavlm_fuse_emit_layout_batch_to": (C.c_int, [vp, C.POINTER(vp), vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64,
+                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
     "mavlm_fuse_emit_layout": (C.c_int, [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64,
                                          C.POINTER(C.c_int64), vp]),
     "mavlm_layout_rows": (C.c_int64, [C.POINTER(Config), i32, i32, i32, i32, i32, i32]),

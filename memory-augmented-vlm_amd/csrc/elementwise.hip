@@ -278,12 +278,15 @@ __global__ __launch_bounds__(256) void row_add_kernel(const uint16_t* __restrict
 // GAP (an instantiation of its own): output row r lands r / gap rows further down - the rows left free are the newline rows
 // of the `grid` / `frame` token layouts (llava_arch.py:330-357), written by copy_rows_kernel
 struct row_add_srcs { const uint16_t* p[16]; };
-template <typename T, bool GAP = false>
+// VB (an instantiation of its own): video b's output starts vb.off[b] elements into `out` instead of b * vstride
+template <typename T, bool GAP = false, bool VB = false>
 __global__ __launch_bounds__(256) void row_add_batch_kernel(row_add_srcs xs, const int64_t* __restrict__ src,
                                                             const uint16_t* __restrict__ table, uint16_t* __restrict__ out,
-                                                            long long vstride, int T_, int P, int D, int gap) {
+                                                            long long vstride, int T_, int P, int D, int gap,
+                                                            mavlm_vbase_arg<VB> vb) {
   const uint16_t* __restrict__ x = xs.p[blockIdx.y];
-  out += (size_t)blockIdx.y * vstride;
+  if constexpr (VB) out += (size_t)vb.off[blockIdx.y];
+  else out += (size_t)blockIdx.y * vstride;
   const int dv = D >> 3;
   const size_t total = (size_t)T_ * P * dv;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -323,12 +326,16 @@ struct copy_rows_args {
   long long dst[4];    // first row of run i inside a video's block
   int rep[4];          // 0: n consecutive source rows to consecutive rows; > 0: source row 0 to rows dst, dst + rep, ...
 };
-__global__ __launch_bounds__(256) void copy_rows_kernel(copy_rows_args a, uint16_t* __restrict__ out, long long vstride, int D) {
+template <bool VB = false>
+__global__ __launch_bounds__(256) void copy_rows_kernel(copy_rows_args a, uint16_t* __restrict__ out, long long vstride, int D,
+                                                        mavlm_vbase_arg<VB> vb) {
   int r = blockIdx.x, i = 0;
   while (i < 3 && r >= a.n[i]) r -= a.n[i++];
   const int rp = a.rep[i];
   const u16x8* s = (const u16x8*)(a.src[i] + (rp > 0 ? (size_t)0 : (size_t)r * D));
-  u16x8* d = (u16x8*)(out + (size_t)blockIdx.y * vstride + (size_t)(a.dst[i] + (rp > 0 ? (long long)r * rp : (long long)r)) * D);
+  size_t vo = (size_t)blockIdx.y * vstride;
+  if constexpr (VB) vo = (size_t)vb.off[blockIdx.y];          // (per-video bases instead of the constant stride)
+  u16x8* d = (u16x8*)(out + vo + (size_t)(a.dst[i] + (rp > 0 ? (long long)r * rp : (long long)r)) * D);
   for (int c = threadIdx.x; c < (D >> 3); c += 256) d[c] = s[c];
 }
 
@@ -459,9 +466,11 @@ hipError_t mavlm_launch_row_add(const void* x, const int64_t* src, const void* t
 }
 
 hipError_t mavlm_launch_row_add_batch(const void* const* x, const int64_t* src, const void* table_row, void* out,
-                                      long long vstride, int B, int T_, int P, int D, int dtype, hipStream_t s, int gap) {
+                                      long long vstride, int B, int T_, int P, int D, int dtype, hipStream_t s, int gap,
+                                      const long long* vbase) {
   if (T_ <= 0 || B <= 0) return hipSuccess;
   if (!x || !table_row || !out || P <= 0 || D <= 0 || (D & 7) || gap < 0) return hipErrorInvalidValue;
+  if (vbase && B > MAVLM_VBASE_MAX) return hipErrorInvalidValue;
   const size_t total = (size_t)T_ * P * (D >> 3);
   mavlm_prof_scope prof(MAVLM_K_ROWADD, 0.0, 4.0 * B * T_ * (double)P * D, s);
   size_t blocks = (total + 255) / 256;
@@ -474,13 +483,23 @@ hipError_t mavlm_launch_row_add_batch(const void* const* x, const int64_t* src, 
       xs.p[i] = (const uint16_t*)x[b0 + i];
     }
     uint16_t* o = (uint16_t*)out + (size_t)b0 * vstride;
-#define RAB(TT, GG)                                                                                                    \
-  hipLaunchKernelGGL((row_add_batch_kernel<TT, GG>), dim3((unsigned)blocks, (unsigned)nb), dim3(256), 0, s, xs, src, \
-                     (const uint16_t*)table_row, o, vstride, T_, P, D, gap)
+#define RAB(TT, GG, VV, vb)                                                                                                \
+  hipLaunchKernelGGL((row_add_batch_kernel<TT, GG, VV>), dim3((unsigned)blocks, (unsigned)nb), dim3(256), 0, s, xs, src, \
+                     (const uint16_t*)table_row, o, vstride, T_, P, D, gap, vb)
+    if (vbase) {          // (B <= 16: one pass of this loop)
+      const mavlm_vbase_arg<true> vb = mavlm_vbase_pack(vbase, nb);
+      if (dtype == MAVLM_F16) {
+        if (gap > 0) RAB(F16, true, true, vb); else RAB(F16, false, true, vb);
+      } else {
+        if (gap > 0) RAB(BF16, true, true, vb); else RAB(BF16, false, true, vb);
+      }
+      continue;
+    }
+    const mavlm_vbase_arg<false> vb0 = {};
     if (dtype == MAVLM_F16) {
-      if (gap > 0) RAB(F16, true); else RAB(F16, false);
+      if (gap > 0) RAB(F16, true, false, vb0); else RAB(F16, false, false, vb0);
     } else {
-      if (gap > 0) RAB(BF16, true); else RAB(BF16, false);
+      if (gap > 0) RAB(BF16, true, false, vb0); else RAB(BF16, false, false, vb0);
     }
 #undef RAB
   }
@@ -488,8 +507,8 @@ hipError_t mavlm_launch_row_add_batch(const void* const* x, const int64_t* src, 
 }
 
 hipError_t mavlm_launch_copy_rows(const void* const* src, const int* n, const long long* dst, int runs, void* out,
-                                  long long vstride, int B, int D, hipStream_t s, const int* rep) {
-  if (runs < 0 || runs > 4 || !out || B <= 0 || D <= 0 || (D & 7)) return hipErrorInvalidValue;
+                                  long long vstride, int B, int D, hipStream_t s, const int* rep, const long long* vbase) {
+  if (runs < 0 || runs > 4 || !out || B <= 0 || D <= 0 || (D & 7) || (vbase && B > MAVLM_VBASE_MAX)) return hipErrorInvalidValue;
   copy_rows_args a = {};
   int total = 0, k = 0;
   for (int i = 0; i < runs; ++i) {
@@ -503,7 +522,12 @@ hipError_t mavlm_launch_copy_rows(const void* const* src, const int* n, const lo
   }
   if (!total) return hipSuccess;
   mavlm_prof_scope prof(MAVLM_K_ROWADD, 0.0, 4.0 * total * (double)B * D, s);
-  hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)total, (unsigned)B), dim3(256), 0, s, a, (uint16_t*)out, vstride, D);
+  if (vbase)
+    hipLaunchKernelGGL(copy_rows_kernel<true>, dim3((unsigned)total, (unsigned)B), dim3(256), 0, s, a, (uint16_t*)out, vstride, D,
+                       mavlm_vbase_pack(vbase, B));
+  else
+    hipLaunchKernelGGL(copy_rows_kernel<false>, dim3((unsigned)total, (unsigned)B), dim3(256), 0, s, a, (uint16_t*)out, vstride, D,
+                       mavlm_vbase_arg<false>{});
   return hipGetLastError();
 }
 

@@ -333,6 +333,12 @@ hipError_t mavlm_launch_gemm(const mavlm_gemm_args& g, int dtype, hipStream_t s)
   // gapped output rows: the kernel choice below is the one of c_gap = 0 (same tiles, same split: same bits); where that is
   // a kernel without a row map the caller writes to a scratch and places the rows itself (mavlm_launch_spread_rows)
   if (g.c_gap < 0 || (g.c_gap > 0 && (g.epilogue != MAVLM_EPI_BIAS || !mavlm_gemm_row_map_ok(g)))) return hipErrorInvalidValue;
+  // per-video bases: a row-batched bias-epilogue launch of at most MAVLM_VBASE_MAX videos, 16-byte aligned blocks
+  if (g.c_vbase) {
+    if (g.c_rpb <= 0 || g.epilogue != MAVLM_EPI_BIAS || g.c_nb < 1 || g.c_nb > MAVLM_VBASE_MAX) return hipErrorInvalidValue;
+    for (int b = 0; b < g.c_nb; ++b)
+      if (g.c_vbase[b] < 0 || (g.c_vbase[b] & 7)) return hipErrorInvalidValue;
+  }
   if (g.epilogue == MAVLM_EPI_LN) {
     // dense + residual + LayerNorm in one kernel: the non-persistent 256-column-tile kernel only (its row-block exchange
     // needs the N / 256 workgroups of a row block in flight together)
@@ -356,7 +362,8 @@ hipError_t mavlm_launch_gemm(const mavlm_gemm_args& g, int dtype, hipStream_t s)
     if (use_128x256(g)) return mavlm_launch_gemm128(g, dtype, s);
     const int rows = mavlm_gemm_tile_rows(g.M, g.N);
     const long tiles = (long)((g.M + rows - 1) / rows) * (g.N / 256);
-    if (tiles > 256 && mavlm_gemm256p_supported(g)) return mavlm_launch_gemm256p(g, dtype, s);
+    // (the forced-persistent hook is honoured here as below: it is how a test reaches the persistent kernel on a small grid)
+    if ((tiles > 256 || g_mavlm_gemm_tile == 257) && mavlm_gemm256p_supported(g)) return mavlm_launch_gemm256p(g, dtype, s);
     return mavlm_launch_gemm256(g, dtype, s);
   }
   if (g.splitk_ws != nullptr && g_mavlm_gemm_tile == 0) {

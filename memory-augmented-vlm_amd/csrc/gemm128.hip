@@ -65,13 +65,14 @@ struct IC1 { static constexpr int value = V; };
     __builtin_amdgcn_sched_barrier(0);                         \
   } while (0)
 
-template <typename T, int EPI, bool GAP = false>
+template <typename T, int EPI, bool GAP = false, bool VB = false>
 __global__ __launch_bounds__(256, 2) void gemm128_kernel(const uint16_t* __restrict__ A, int lda,
                                                          const uint16_t* __restrict__ W, int ldw,
                                                          const float* __restrict__ bias,
                                                          const uint16_t* __restrict__ res, int ldr,
                                                          void* __restrict__ Cout, int ldc, int M, int N, int K,
-                                                         int c_rpb, int c_nb, long long c_bs, mavlm_ln_epilogue ln, int c_gap) {
+                                                         int c_rpb, int c_nb, long long c_bs, mavlm_ln_epilogue ln, int c_gap,
+                                                         mavlm_vbase_arg<VB> vb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -410,6 +411,10 @@ __global__ __launch_bounds__(256, 2) void gemm128_kernel(const uint16_t* __restr
   auto crow = [&](int m) -> size_t {
     if (c_rpb <= 0) return (size_t)(GAP ? m + m / c_gap : m) * ldc;
     const int q = m / c_rpb, r = m - q * c_rpb;
+    if constexpr (VB) {      // per-video bases (mavlm_gemm_args::c_vbase): one 8-byte read of the argument block per row
+      const int v = (q / c_nb) * c_rpb + r;
+      return (size_t)vb.off[q % c_nb] + (size_t)(GAP ? v + v / c_gap : v) * ldc;
+    }
     if (!GAP) return (size_t)(q % c_nb) * (size_t)c_bs + ((size_t)(q / c_nb) * c_rpb + r) * ldc;
     const int v = (q / c_nb) * c_rpb + r;
     return (size_t)(q % c_nb) * (size_t)c_bs + (size_t)(v + v / c_gap) * ldc;
@@ -446,9 +451,11 @@ __global__ __launch_bounds__(256, 2) void gemm128_kernel(const uint16_t* __restr
   }
 }
 
-template <typename T, int EPI, bool GAP = false>
+template <typename T, int EPI, bool GAP = false, bool VB = false>
 hipError_t launch128(const mavlm_gemm_args& g, hipStream_t s) {
-  auto kern = gemm128_kernel<T, EPI, GAP>;
+  auto kern = gemm128_kernel<T, EPI, GAP, VB>;
+  mavlm_vbase_arg<VB> vb = {};
+  if constexpr (VB) vb = mavlm_vbase_pack(g.c_vbase, g.c_nb);
   static mavlm_per_device_once once;
   {
     hipError_t e = once.dyn_lds((const void*)kern, GEMM128_LDS);
@@ -457,12 +464,16 @@ hipError_t launch128(const mavlm_gemm_args& g, hipStream_t s) {
   const int ntm = (g.M + BM1 - 1) / BM1, ntn = g.N / BN1;
   hipLaunchKernelGGL(kern, dim3(ntm * ntn), dim3(256), GEMM128_LDS, s, (const uint16_t*)g.A, g.lda, (const uint16_t*)g.W,
                      g.ldw, g.bias, (const uint16_t*)g.res, g.ldr, g.C, g.ldc, g.M, g.N, g.K, g.c_rpb, g.c_nb > 0 ? g.c_nb : 1,
-                     (long long)g.c_bstride, g.ln, g.c_gap);
+                     (long long)g.c_bstride, g.ln, g.c_gap, vb);
   return hipGetLastError();
 }
 
 template <typename T>
 hipError_t launch128_epi(const mavlm_gemm_args& g, hipStream_t s) {
+  if (g.c_vbase) {        // per-video bases: the bias epilogue only (see gemm256.hip launch256)
+    if (g.epilogue != MAVLM_EPI_BIAS) return hipErrorInvalidValue;
+    return g.c_gap > 0 ? launch128<T, MAVLM_EPI_BIAS, true, true>(g, s) : launch128<T, MAVLM_EPI_BIAS, false, true>(g, s);
+  }
   if (g.c_gap > 0)        // gapped output rows: the bias epilogue only (see gemm256.hip launch256)
     return g.epilogue == MAVLM_EPI_BIAS ? launch128<T, MAVLM_EPI_BIAS, true>(g, s) : hipErrorInvalidValue;
   switch (g.epilogue) {

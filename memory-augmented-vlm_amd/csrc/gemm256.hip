@@ -75,14 +75,14 @@ __device__ __forceinline__ float gelu_erf2(float x) { return 0.5f * x * (1.0f + 
 // The LDS image keeps its 128-row half-tile slots (rows 112-127 of a slot are staged but never read), so the DMA
 // instruction count - and with it every counted vmcnt - is the same for both heights.  Each output element sums its
 // K products in the same order for both heights: results are bit-identical.
-template <typename T, int EPI, int MT1, bool GAP = false>
+template <typename T, int EPI, int MT1, bool GAP = false, bool VB = false>
 __global__ __launch_bounds__(512, 2) void gemm256_kernel(const uint16_t* __restrict__ A, int lda,
                                                          const uint16_t* __restrict__ W, int ldw,
                                                          const float* __restrict__ bias,
                                                          const uint16_t* __restrict__ res, int ldr,
                                                          void* __restrict__ Cout, int ldc, int M, int N, int K,
                                                          int c_rpb, int c_nb, long long c_bs, mavlm_ln_epilogue ln,
-                                                         int ksplit, int c_gap) {
+                                                         int ksplit, int c_gap, mavlm_vbase_arg<VB> vb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -422,6 +422,10 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const uint16_t* __restr
   auto crow = [&](int m) -> size_t {
     if (c_rpb <= 0) return (size_t)(GAP ? m + m / c_gap : m) * ldc;
     const int q = m / c_rpb, r = m - q * c_rpb;
+    if constexpr (VB) {      // per-video bases (mavlm_gemm_args::c_vbase): one 8-byte read of the argument block per row
+      const int v = (q / c_nb) * c_rpb + r;
+      return (size_t)vb.off[q % c_nb] + (size_t)(GAP ? v + v / c_gap : v) * ldc;
+    }
     if (!GAP) return (size_t)(q % c_nb) * (size_t)c_bs + ((size_t)(q / c_nb) * c_rpb + r) * ldc;
     const int v = (q / c_nb) * c_rpb + r;
     return (size_t)(q % c_nb) * (size_t)c_bs + (size_t)(v + v / c_gap) * ldc;
@@ -459,9 +463,11 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const uint16_t* __restr
   }
 }
 
-template <typename T, int EPI, int MT1, bool GAP = false>
+template <typename T, int EPI, int MT1, bool GAP = false, bool VB = false>
 hipError_t launch256h(const mavlm_gemm_args& g, hipStream_t s, int splits = 1, int ksplit = 0) {
-  auto kern = gemm256_kernel<T, EPI, MT1, GAP>;
+  auto kern = gemm256_kernel<T, EPI, MT1, GAP, VB>;
+  mavlm_vbase_arg<VB> vb = {};
+  if constexpr (VB) vb = mavlm_vbase_pack(g.c_vbase, g.c_nb);
   constexpr int BMT = 2 * (64 + 16 * MT1);
   static mavlm_per_device_once once;
   {
@@ -471,12 +477,19 @@ hipError_t launch256h(const mavlm_gemm_args& g, hipStream_t s, int splits = 1, i
   const int ntm = (g.M + BMT - 1) / BMT, ntn = g.N / BN2;
   hipLaunchKernelGGL(kern, dim3(ntm * ntn, splits), dim3(512), GEMM256_LDS, s, (const uint16_t*)g.A, g.lda, (const uint16_t*)g.W,
                      g.ldw, g.bias, (const uint16_t*)g.res, g.ldr, g.C, g.ldc, g.M, g.N, g.K, g.c_rpb, g.c_nb > 0 ? g.c_nb : 1,
-                     (long long)g.c_bstride, g.ln, ksplit, g.c_gap);
+                     (long long)g.c_bstride, g.ln, ksplit, g.c_gap, vb);
   return hipGetLastError();
 }
 
 template <typename T, int EPI>
 hipError_t launch256(const mavlm_gemm_args& g, hipStream_t s) {
+  if (g.c_vbase) {        // per-video bases (mavlm_gemm_args::c_vbase): the bias epilogue only, with and without the gap
+    if (EPI != MAVLM_EPI_BIAS) return hipErrorInvalidValue;
+    constexpr int E = MAVLM_EPI_BIAS;
+    const bool h224 = mavlm_gemm_tile_rows(g.M, g.N) == 224;
+    if (g.c_gap > 0) return h224 ? launch256h<T, E, 3, true, true>(g, s) : launch256h<T, E, 4, true, true>(g, s);
+    return h224 ? launch256h<T, E, 3, false, true>(g, s) : launch256h<T, E, 4, false, true>(g, s);
+  }
   if (g.c_gap > 0) {      // gapped output rows (mavlm_gemm_args::c_gap): the bias epilogue only - the Memory-Fuser's second GEMM
     if (EPI != MAVLM_EPI_BIAS) return hipErrorInvalidValue;
     constexpr int E = MAVLM_EPI_BIAS;

@@ -65,12 +65,13 @@ constexpr int GEMM256P_LDS = GEMM256_LDS + 2048;
 __device__ __forceinline__ float gelu_erf2p(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 // MT1: 4 -> 256-row tiles, 3 -> 224-row tiles (see gemm256_kernel)
-template <typename T, int EPI, int MT1, bool GAP = false>
+template <typename T, int EPI, int MT1, bool GAP = false, bool VB = false>
 __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const uint16_t* __restrict__ A, int lda,
                                                           const uint16_t* __restrict__ W, int ldw,
                                                           const float* __restrict__ bias, void* __restrict__ Cout,
                                                           int ldc, int M, int N, int K, int total_tiles, int c_rpb,
-                                                          int c_nb, long long c_bs, int g_order, int c_gap) {
+                                                          int c_nb, long long c_bs, int g_order, int c_gap,
+                                                          mavlm_vbase_arg<VB> vb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -268,6 +269,10 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const uint16_t* __rest
     auto crow = [&](int m) -> size_t {
       if (c_rpb <= 0) return (size_t)(GAP ? m + m / c_gap : m) * ldc;
       const int q = m / c_rpb, r = m - q * c_rpb;
+      if constexpr (VB) {      // per-video bases (mavlm_gemm_args::c_vbase): one 8-byte read of the argument block per row
+        const int v = (q / c_nb) * c_rpb + r;
+        return (size_t)vb.off[q % c_nb] + (size_t)(GAP ? v + v / c_gap : v) * ldc;
+      }
       if (!GAP) return (size_t)(q % c_nb) * (size_t)c_bs + ((size_t)(q / c_nb) * c_rpb + r) * ldc;
       const int v = (q / c_nb) * c_rpb + r;
       return (size_t)(q % c_nb) * (size_t)c_bs + (size_t)(v + v / c_gap) * ldc;
@@ -315,9 +320,11 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const uint16_t* __rest
 #undef MAVLM_QUADRANT
 }
 
-template <typename T, int EPI, int MT1, bool GAP = false>
+template <typename T, int EPI, int MT1, bool GAP = false, bool VB = false>
 hipError_t launch256ph(const mavlm_gemm_args& g, hipStream_t s) {
-  auto kern = gemm256p_kernel<T, EPI, MT1, GAP>;
+  auto kern = gemm256p_kernel<T, EPI, MT1, GAP, VB>;
+  mavlm_vbase_arg<VB> vb = {};
+  if constexpr (VB) vb = mavlm_vbase_pack(g.c_vbase, g.c_nb);
   constexpr int BMT = 2 * (64 + 16 * MT1);
   static mavlm_per_device_once once;
   static int cus = 0;          // MI355X: 256 on every device of a node
@@ -336,12 +343,19 @@ hipError_t launch256ph(const mavlm_gemm_args& g, hipStream_t s) {
   const int grid = tiles < cus ? tiles : cus;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), GEMM256P_LDS, s, (const uint16_t*)g.A, g.lda, (const uint16_t*)g.W,
                      g.ldw, g.bias, g.C, g.ldc, g.M, g.N, g.K, tiles, g.c_rpb, g.c_nb > 0 ? g.c_nb : 1, (long long)g.c_bstride,
-                     g_mavlm_gemm_order, g.c_gap);
+                     g_mavlm_gemm_order, g.c_gap, vb);
   return hipGetLastError();
 }
 
 template <typename T, int EPI>
 hipError_t launch256p(const mavlm_gemm_args& g, hipStream_t s) {
+  if (g.c_vbase) {        // per-video bases: the bias epilogue only (see gemm256.hip launch256)
+    if (EPI != MAVLM_EPI_BIAS) return hipErrorInvalidValue;
+    constexpr int E = MAVLM_EPI_BIAS;
+    const bool h224 = mavlm_gemm_tile_rows(g.M, g.N) == 224;
+    if (g.c_gap > 0) return h224 ? launch256ph<T, E, 3, true, true>(g, s) : launch256ph<T, E, 4, true, true>(g, s);
+    return h224 ? launch256ph<T, E, 3, false, true>(g, s) : launch256ph<T, E, 4, false, true>(g, s);
+  }
   if (g.c_gap > 0) {      // gapped output rows: the bias epilogue only (see gemm256.hip launch256)
     if (EPI != MAVLM_EPI_BIAS) return hipErrorInvalidValue;
     constexpr int E = MAVLM_EPI_BIAS;

@@ -898,7 +898,8 @@ inline int64_t block_rows(int64_t rows, int32_t layout, int gap) {
 
 int fuse_emit_impl(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_idx, int32_t n_fine, const void* mem_prompt,
                    int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt, const void* newline,
-                   int32_t with_frames, int32_t layout, void* out, int64_t cap_rows, int64_t* rows, hipStream_t s) {
+                   int32_t with_frames, int32_t layout, void* out, int64_t cap_rows, int64_t* rows, hipStream_t s,
+                   const int64_t* dst_row = nullptr) {
   if (!x->w.w_f1 || !x->w.b_f1 || !x->w.w_f2 || !x->w.b_f2_type0 || (with_frames && !x->w.type1)) return MAVLM_E_STATE;
   if (n_mem_prompt < 0 || n_frame_prompt < 0 || n_fine < 0 || (n_mem_prompt && !mem_prompt) ||
       (with_frames && ((n_frame_prompt && !frame_prompt) || (n_fine && (!x_pe || !fine_idx)))))
@@ -915,6 +916,21 @@ int fuse_emit_impl(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_id
   const int64_t r_fp = r_mem + mem_rows, r_fine = r_fp + n_frame_prompt, fine_rows = block_rows((int64_t)n_fine * c.patches, layout, gap);
   const int64_t need = with_frames ? r_fine + fine_rows : r_fp;
   if (cap_rows < need) return MAVLM_E_ARG;
+  // dst_row (mavlm_fuse_emit_layout_batch_to; cap_rows = rows of `out`): video b's block starts at row dst_row[b] instead of
+  // b * cap_rows.  Checked here, on the host, before the first launch: inside `out`, pairwise disjoint.  The bases go to the
+  // kernels by value, as element offsets (mavlm_gemm_args::c_vbase).
+  long long vbase_[MAVLM_VBASE_MAX];
+  const long long* vbase = nullptr;
+  if (dst_row) {
+    if (B > MAVLM_VBASE_MAX) return MAVLM_E_ARG;
+    for (int b = 0; b < B; ++b) {
+      if (dst_row[b] < 0 || dst_row[b] > cap_rows - need) return MAVLM_E_ARG;
+      for (int a = 0; a < b; ++a)
+        if (dst_row[a] < dst_row[b] + need && dst_row[b] < dst_row[a] + need) return MAVLM_E_ARG;
+      vbase_[b] = (long long)dst_row[b] * D;
+    }
+    vbase = vbase_;
+  }
   if (with_frames && n_fine)
     for (int b = 0; b < B; ++b)
       if (!x_pe[b]) return MAVLM_E_ARG;
@@ -930,7 +946,7 @@ int fuse_emit_impl(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_id
     const long long dst[4] = {0, r_mem + (gap > 0 ? gap : (int64_t)n * R1), r_fp, r_fine + (gap > 0 ? gap : (int64_t)n_fine * c.patches)};
     const int rep[4] = {0, gap > 0 ? gap + 1 : 0, 0, gap > 0 ? gap + 1 : 0};
     if ((((uintptr_t)mem_prompt | (uintptr_t)newline | (uintptr_t)frame_prompt | (uintptr_t)out) & 15)) return MAVLM_E_ARG;
-    MAVLM_TRY(mavlm_launch_copy_rows(src, cnt, dst, 4, out, (long long)cap_rows * D, B, D, s, rep));
+    MAVLM_TRY(mavlm_launch_copy_rows(src, cnt, dst, 4, out, (long long)cap_rows * D, B, D, s, rep, vbase));
   }
   const int oldest = x->steps <= cap ? 0 : x->steps % cap;
   // torch.cat(memory_cache) order = oldest first (llava_arch.py:545) = ring slots oldest..cap-1, then 0..oldest-1: at most
@@ -951,6 +967,7 @@ int fuse_emit_impl(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_id
     if (B > 1) {
       g.splitk_ws = nullptr;
       g.c_rpb = R1; g.c_nb = B; g.c_bstride = (long long)cap_rows * D;
+      g.c_vbase = vbase;
     }
     if (gap > 0 && !mavlm_gemm_row_map_ok(g)) {
       // the writer this shape takes has no row map (128^2 kernel / split-K reduce; single videos on small grids): the same
@@ -967,7 +984,7 @@ int fuse_emit_impl(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_id
   }
   if (with_frames && n_fine)
     MAVLM_TRY(mavlm_launch_row_add_batch(x_pe, fine_idx, x->w.type1, o + (size_t)r_fine * rowb, (long long)cap_rows * D, B, n_fine,
-                                         c.patches, D, dt, s, gap));
+                                         c.patches, D, dt, s, gap, vbase));
   *rows = need;
   return 0;
 }
@@ -991,6 +1008,17 @@ int mavlm_fuse_emit_layout_batch(mavlm_ctx* x, const void* const* x_pe, const in
   if (!x->has_w || !x->has_b) return MAVLM_E_STATE;
   return fuse_emit_impl(x, x_pe, fine_idx, n_fine, mem_prompt, n_mem_prompt, frame_prompt, n_frame_prompt, newline, with_frames,
                         layout, out, rows_per_video, rows, (hipStream_t)stream);
+}
+
+int mavlm_fuse_emit_layout_batch_to(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_idx, int32_t n_fine,
+                                    const void* mem_prompt, int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt,
+                                    const void* newline, int32_t with_frames, int32_t layout, void* out, int64_t out_rows,
+                                    const int64_t* dst_row, int64_t* rows, void* stream) {
+  if (!x || !out || !rows || !dst_row || out_rows < 0) return MAVLM_E_ARG;
+  if (!x->has_w || !x->has_b) return MAVLM_E_STATE;
+  if (nbatch(x->cfg) < 2) return MAVLM_E_STATE;             // (a single video: mavlm_fuse_emit_layout writes where `out` points)
+  return fuse_emit_impl(x, x_pe, fine_idx, n_fine, mem_prompt, n_mem_prompt, frame_prompt, n_frame_prompt, newline, with_frames,
+                        layout, out, out_rows, rows, (hipStream_t)stream, dst_row);
 }
 
 int mavlm_fuse_emit(mavlm_ctx* x, const void* x_pe, const int64_t* fine_idx, int32_t n_fine, const void* mem_prompt,

@@ -42,8 +42,22 @@ struct mavlm_gemm_args {
   // writes.  Same tiles and same arithmetic as c_gap = 0: only the destination differs.  A launch that mavlm_launch_gemm
   // would run on a kernel without a row map (mavlm_gemm_row_map_ok() false) is refused (hipErrorInvalidValue).
   int c_gap = 0;
+  // Per-video bases (row-batched output, bias epilogue; null = the constant stride above): HOST array of c_nb element offsets,
+  // batch element b's output starts at C + c_vbase[b] instead of C + b * c_bstride (c_nb <= MAVLM_VBASE_MAX; the offsets are
+  // multiples of 8).  They travel to the kernel by value (mavlm_vbase_arg): no copy, no table.  Same tiles and arithmetic again.
+  const long long* c_vbase = nullptr;
   mavlm_ln_epilogue ln;          // EPI_LN only
 };
+// The per-video bases as a kernel argument: an instantiation that takes none (VB = false, every kernel that existed before the
+// bases) gets an empty argument and the parameter list it had.
+#define MAVLM_VBASE_MAX 16
+template <bool VB> struct mavlm_vbase_arg {};
+template <> struct mavlm_vbase_arg<true> { long long off[MAVLM_VBASE_MAX]; };
+inline mavlm_vbase_arg<true> mavlm_vbase_pack(const long long* v, int n) {
+  mavlm_vbase_arg<true> a = {};
+  for (int i = 0; i < n && i < MAVLM_VBASE_MAX; ++i) a.off[i] = v[i];
+  return a;
+}
 // wide: 1 = rows of up to 4096 columns (test mode), 0 = up to 1024, -1 = the process-wide hook g_mavlm_gemm_ln_wide
 bool mavlm_gemm_ln_supported(int M, int N, int K, int wide = -1);
 extern int g_mavlm_gemm_ln_wide;
@@ -255,14 +269,18 @@ hipError_t mavlm_launch_row_add(const void* x, const int64_t* src, const void* t
 // device pointers; vstride in elements)
 // gap > 0: output row r of a video lands r / gap rows further down (the newline rows of a token layout, see c_gap)
 hipError_t mavlm_launch_row_add_batch(const void* const* x, const int64_t* src, const void* table_row, void* out,
-                                      long long vstride, int B, int T, int P, int D, int dtype, hipStream_t s, int gap = 0);
+                                      long long vstride, int B, int T, int P, int D, int dtype, hipStream_t s, int gap = 0,
+                                      const long long* vbase = nullptr);
 
 // `runs` (<= 4) literal row runs: out[b*vstride + (dst[i]+r)*D ..] = src[i][r*D ..] for r < n[i], every video b < B
 // (vstride in elements); one launch for the prompt / newline rows of mavlm_fuse_emit
+// vbase (both launches here; null = the constant stride): HOST array of B <= MAVLM_VBASE_MAX element offsets, video b's block
+// starts vbase[b] elements into `out` instead of b * vstride (mavlm_gemm_args::c_vbase)
 // rep (null = all 0): run i with rep[i] > 0 is ONE source row written n[i] times, every rep[i] rows from dst[i] on (the newline
 // rows of the `grid` / `frame` layouts: period gap + 1)
 hipError_t mavlm_launch_copy_rows(const void* const* src, const int* n, const long long* dst, int runs, void* out,
-                                  long long vstride, int B, int D, hipStream_t s, const int* rep = nullptr);
+                                  long long vstride, int B, int D, hipStream_t s, const int* rep = nullptr,
+                                  const long long* vbase = nullptr);
 // out[(r + r / gap) * D ..] = in[r * D ..] for r < rows (16-bit rows of D elements, D % 8 == 0; gap > 0): places the contiguous
 // rows of a writer without a row map (mavlm_gemm_row_map_ok() false) into a gapped token block
 hipError_t mavlm_launch_spread_rows(const void* in, void* out, long long rows, int D, int gap, hipStream_t s);

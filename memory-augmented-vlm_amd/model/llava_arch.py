@@ -12,6 +12,9 @@ Mirrors the memory-specific parts of the reference's llava/model/llava_arch.py s
                             PE add -> chunk loop (mavlm_step) -> fuser MLP + type add + prompts/newlines concat
                             (mavlm_fuse_emit_layout) written straight into one token block, in the layout
                             `token_layout(config)` reads from mm_patch_merge_type / mm_newline_position.
+  run_video_groups          several videos of one forward (one per sample): equal sampled lengths step together as row batches,
+                            each block emitted at its place in the padded inputs_embeds buffer (`VideoPlacement`,
+                            mavlm_fuse_emit_layout_batch_to); the reference serves one video per forward (llava_arch.py:436).
 
 Non-video inputs behave as in the reference (round 3): a plain image batch takes the reference's tensor branch (:703,
 backbone ops, restated in torch); a list without a video fails as the reference's memory loop does (IndexError); images
@@ -277,15 +280,40 @@ def video_memory_tokens(model, image: torch.Tensor, frame_idx_cpu: torch.Tensor,
     return out, info
 
 
+def _batch_pe_frames(pe, images, frame_idx_cpu, T):
+    """PE-added frames of the videos of a row batch (llava_arch.py:510-511).  `frame_idx_cpu`: one index tensor shared by the
+    videos, or a list of one per video, all of length T (two videos of 130 and 150 input frames both sample 128 frames, at
+    other original indices): the gather runs per video either way."""
+    if isinstance(frame_idx_cpu, (list, tuple)):
+        if len(frame_idx_cpu) != len(images) or any(i.numel() != T for i in frame_idx_cpu):
+            raise capi.MavlmError(f"row batch: one frame index tensor of {T} entries per video expected")
+        idxs = list(frame_idx_cpu)
+    else:
+        idxs = [frame_idx_cpu] * len(images)
+    dev = images[0].device
+    xs, last, last_dev = [], None, None
+    for im, idx in zip(images, idxs):
+        if idx is not last:
+            pe.check_indices(idx)
+            last, last_dev = idx, _device_indices(idx, dev)
+        xs.append(pe(im, last_dev, indices_checked=True))
+    return xs
+
+
 @torch.no_grad()
-def video_memory_tokens_batched(model, bp: BatchedProjector, images, frame_idx_cpu: torch.Tensor,
+def video_memory_tokens_batched(model, bp: BatchedProjector, images, frame_idx_cpu,
                                 memory_prompt_embeds: torch.Tensor, frame_prompt_embeds: torch.Tensor,
                                 image_newline: Optional[torch.Tensor], with_frames: bool = True, chunk: int = 32,
-                                fine_frames: int = 32, out: Optional[torch.Tensor] = None, layout: str = "one_token"):
+                                fine_frames: int = 32, out: Optional[torch.Tensor] = None, layout: str = "one_token",
+                                dst_rows: Optional[List[int]] = None):
     """`video_memory_tokens` for B videos of the SAME length stepped together (row batch, `BatchedProjector`): every
     weight-shared GEMM / LayerNorm of the path runs once over the stacked memory rows of all videos.  `images`: B tensors
     [T,196,D]; `frame_idx_cpu`: the original frame indices (shared: same length, same sampling).  Returns
-    (tokens [B, rows, D] - video b's block is tokens[b] -, info).  Inference only.  `layout`: as video_memory_tokens."""
+    (tokens [B, rows, D] - video b's block is tokens[b] -, info).  Inference only.  `layout`: as video_memory_tokens.
+    `frame_idx_cpu` may be a list of B index tensors of one length (_batch_pe_frames).
+    `dst_rows` (with `out` = a contiguous [out_rows, D] buffer, e.g. the padded inputs_embeds of a batch of samples seen as
+    rows): video b's block is written at row dst_rows[b] of `out` (mavlm_fuse_emit_layout_batch_to: the same launches, one
+    destination per video; rows outside the blocks are not touched); returns (out, info) with info["block_rows"]."""
     layout_period(layout, images[0].shape[1])
     B = bp.batch
     if len(images) != B:
@@ -297,9 +325,7 @@ def video_memory_tokens_batched(model, bp: BatchedProjector, images, frame_idx_c
     pe: TemporalPositionalEncoding = model.positional_encoding
     rm: TransformerProjector = model.recurrent_memory_transformer
     dev, dt = images[0].device, images[0].dtype
-    pe.check_indices(frame_idx_cpu)
-    idx_dev = _device_indices(frame_idx_cpu, dev)
-    xs = [pe(im, idx_dev, indices_checked=True) for im in images]                           # :510-511
+    xs = _batch_pe_frames(pe, images, frame_idx_cpu, T)                                     # :510-511
     fine_cpu = fine_frame_indices(T, fine_frames)                                          # :513-522
     bounds = uniform_segment_variant(T, chunk)                                             # :528
     bp.reset()                                                                             # :532
@@ -313,7 +339,12 @@ def video_memory_tokens_batched(model, bp: BatchedProjector, images, frame_idx_c
     rows = memory_prompt_embeds.shape[0] + mem_rows
     if with_frames:
         rows += frame_prompt_embeds.shape[0] + layout_block_rows(n_fine * P, layout, P)
-    if out is None:
+    if dst_rows is not None:
+        if out is None or out.dim() != 2 or out.shape[1] != D or out.dtype != dt or not out.is_contiguous() or not out.is_cuda \
+                or len(dst_rows) != B:
+            raise capi.MavlmError(f"video_memory_tokens_batched: `dst_rows` needs {B} rows of a contiguous [out_rows,{D}] {dt} "
+                                  "GPU tensor `out`")
+    elif out is None:
         out = torch.empty((B, rows, D), device=dev, dtype=dt)
     elif tuple(out.shape) != (B, rows, D) or out.dtype != dt or not out.is_contiguous() or not out.is_cuda:
         raise capi.MavlmError(f"video_memory_tokens_batched: `out` must be a contiguous [{B},{rows},{D}] {dt} GPU tensor")
@@ -323,18 +354,27 @@ def video_memory_tokens_batched(model, bp: BatchedProjector, images, frame_idx_c
     import ctypes
     written = ctypes.c_int64(0)
     xptrs = (capi.vp * B)(*[x.data_ptr() for x in xs])
+    info = {"num_memories": n, "pe_frames": xs, "fine_idx": fine_cpu, "block_rows": rows,
+            "memory_rows": (mp.shape[0], mp.shape[0] + (mem_rows if layout_period(layout, P) else n * R)),
+            "frame_scores": bp.frame_scores}
+    if dst_rows is not None:
+        dst = (ctypes.c_int64 * B)(*[int(r) for r in dst_rows])
+        capi.check(capi.lib().mavlm_fuse_emit_layout_batch_to(eng.ctx, xptrs, _device_indices(fine_cpu, dev).data_ptr(), n_fine,
+                                                              mp.data_ptr(), mp.shape[0], fp.data_ptr(), fp.shape[0], nl_ptr,
+                                                              1 if with_frames else 0, capi.LAYOUTS[layout], out.data_ptr(),
+                                                              out.shape[0], dst, ctypes.byref(written), ops.stream_ptr()),
+                   "mavlm_fuse_emit_layout_batch_to")
+        assert written.value == rows
+        return out, info
     capi.check(capi.lib().mavlm_fuse_emit_layout_batch(eng.ctx, xptrs, _device_indices(fine_cpu, dev).data_ptr(), n_fine,
                                                        mp.data_ptr(), mp.shape[0], fp.data_ptr(), fp.shape[0], nl_ptr,
                                                        1 if with_frames else 0, capi.LAYOUTS[layout], out.data_ptr(), rows,
                                                        ctypes.byref(written), ops.stream_ptr()), "mavlm_fuse_emit_layout_batch")
     assert written.value == rows
-    info = {"num_memories": n, "pe_frames": xs, "fine_idx": fine_cpu,
-            "memory_rows": (mp.shape[0], mp.shape[0] + (mem_rows if layout_period(layout, P) else n * R)),
-            "frame_scores": bp.frame_scores}
     return out, info
 
 
-def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame_idx_cpu: torch.Tensor,
+def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame_idx_cpu,
                                       memory_prompt_embeds: torch.Tensor, frame_prompt_embeds: torch.Tensor,
                                       image_newline: Optional[torch.Tensor], with_frames: bool = True, chunk: int = 32,
                                       fine_frames: int = 32, layout: str = "one_token"):
@@ -342,7 +382,8 @@ def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame
     `BatchedProjector.step_train`, then the tail of `_video_memory_tokens_autograd` over all videos - the fuser MLP runs ONCE
     over the B * n * M * 196 stacked memory rows (HIP autograd Functions); the token-type adds, the layout and the concatenation
     are torch ops, so autograd routes the gradients of token_type_embedding, the prompt embeddings and image_newline as in the
-    reference.  Returns (tokens [B, rows, D] with grad - the bits of `video_memory_tokens_batched` -, info)."""
+    reference.  Returns (tokens [B, rows, D] with grad - the bits of `video_memory_tokens_batched` -, info).
+    `frame_idx_cpu`: shared, or a list of one index tensor per video (_batch_pe_frames)."""
     from .. import _autograd as ag
     layout_period(layout, images[0].shape[1])
     B = bp.batch
@@ -355,9 +396,7 @@ def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame
     pe: TemporalPositionalEncoding = model.positional_encoding
     rm: TransformerProjector = model.recurrent_memory_transformer
     dev, dt = images[0].device, images[0].dtype
-    pe.check_indices(frame_idx_cpu)
-    idx_dev = _device_indices(frame_idx_cpu, dev)
-    xs = [pe(im, idx_dev, indices_checked=True) for im in images]                           # :510-511
+    xs = _batch_pe_frames(pe, images, frame_idx_cpu, T)                                     # :510-511
     fine_cpu = fine_frame_indices(T, fine_frames)                                          # :513-522
     bounds = uniform_segment_variant(T, chunk)                                             # :528
     bp.reset()                                                                             # :532
@@ -386,6 +425,165 @@ def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame
             "memory_rows": (mp.shape[0], mp.shape[0] + (mem_rows if layout_period(layout, P) else n * R)),
             "frame_scores": bp.frame_scores}
     return torch.stack(toks), info
+
+
+ROW_BATCH_SIZES = (8, 4, 2)
+
+
+def plan_row_batches(keys, sizes=ROW_BATCH_SIZES):
+    """Which videos of a forward step together.  `keys`: one hashable per video, in input order (the sampled frame count, with
+    whatever else has to agree inside a row batch); videos with equal keys form a group, consecutive or not.  A group is cut
+    into row batches of the sizes in `sizes`, largest first; what is left of it runs as single videos.  Returns
+    (batches, singles): lists of input positions (a batch in input order, the batches in the order of their first video), and
+    the positions of the singles, ascending.  Three sizes bound the number of batched engines a model keeps; the batched emit
+    takes at most 16 videos per launch."""
+    sizes = sorted({int(s) for s in sizes}, reverse=True)
+    if any(s < 2 or s > 16 for s in sizes):
+        raise ValueError("row batch sizes: 2 .. 16 videos")
+    groups = {}
+    for i, k in enumerate(keys):
+        groups.setdefault(k, []).append(i)
+    batches, singles = [], []
+    for members in groups.values():
+        at = 0
+        for s in sizes:
+            while len(members) - at >= s:
+                batches.append(members[at:at + s])
+                at += s
+        singles += members[at:]
+    batches.sort(key=lambda b: b[0])
+    return batches, sorted(singles)
+
+
+class VideoPlacement:
+    """Where everything of a batch of samples lands in the padded [B, Lmax, D] `inputs_embeds` buffer when each video block is
+    emitted in place - what `splice_into_text` arrives at by concatenating and padding, computed on the host from the token ids
+    alone.  Fields:
+      general     True: a sample is longer than tokenizer_model_max_length (the cut may fall into a block): take the general
+                  path (`splice_into_text`); only `lengths` and `Lmax` (after the cut) are filled in then
+      Lmax        padded length;  lengths[s]: rows of sample s;  starts[s]: its first row (left padding: Lmax - lengths[s])
+      video_of[s] the video of sample s (-1: text only);  image_at[s]: position of its image token among its ids (-1)
+      dst_row[v]  first row of video v's block in the buffer seen as [B * Lmax, D]
+      segments    (sample, first id, end id, first row inside the sample's Lmax rows): runs of text ids -> rows
+      padding     (sample, first row, end row): rows left zero
+    """
+
+    def __init__(self, ids_list, block_rows, left=False, max_tok=None):
+        ids_list = [i.tolist() if torch.is_tensor(i) else list(i) for i in ids_list]
+        self.block_rows = [int(r) for r in block_rows]
+        self.video_of, self.image_at, self.lengths = [], [], []
+        v = 0
+        for ids in ids_list:
+            at = [i for i, t in enumerate(ids) if t == IMAGE_TOKEN_INDEX]
+            if len(at) > 1 or (at and v >= len(block_rows)):
+                raise NotImplementedError(_ONE_VIDEO_PER_SAMPLE)
+            self.video_of.append(v if at else -1)
+            self.image_at.append(at[0] if at else -1)
+            self.lengths.append(len(ids) - 1 + int(block_rows[v]) if at else len(ids))
+            v += len(at)
+        if v != len(block_rows):
+            raise NotImplementedError(_ONE_VIDEO_PER_SAMPLE)
+        self.general = max_tok is not None and any(n > max_tok for n in self.lengths)
+        if self.general:
+            self.lengths = [min(n, max_tok) for n in self.lengths]
+        self.left = bool(left)
+        self.Lmax = L = max(self.lengths)
+        self.starts = [L - n if self.left else 0 for n in self.lengths]
+        self.dst_row, self.segments, self.padding = [0] * len(block_rows), [], []
+        if self.general:
+            return
+        for s, ids in enumerate(ids_list):
+            st, n, p = self.starts[s], self.lengths[s], self.image_at[s]
+            if n < L:
+                self.padding.append((s, 0, st) if self.left else (s, n, L))
+            if p < 0:
+                if n:
+                    self.segments.append((s, 0, n, st))
+                continue
+            rows = int(block_rows[self.video_of[s]])
+            self.dst_row[self.video_of[s]] = s * L + st + p
+            if p:
+                self.segments.append((s, 0, p, st))
+            if p + 1 < len(ids):
+                self.segments.append((s, p + 1, len(ids), st + p + rows))
+
+    def labels_mask_positions(self, lab_list, attention_mask, position_ids):
+        """(labels [B, Lmax] or None when `lab_list` is None, attention mask or None, position ids or None) as `splice_into_text`
+        builds them (llava_arch.py:745-878): IGNORE_INDEX over every block and the padding, mask True and positions 0..n-1 over
+        a sample's rows, zeros in the padding.  `lab_list`: the labels of each sample's ids (padding removed)."""
+        B, L = len(self.lengths), self.Lmax
+        labels = mask = pos = None
+        if lab_list is not None:
+            labels = torch.full((B, L), IGNORE_INDEX, dtype=lab_list[0].dtype, device=lab_list[0].device)
+            for s, lo, hi, row in self.segments:
+                labels[s, row:row + hi - lo] = lab_list[s][lo:hi]
+        if attention_mask is not None:
+            mask = torch.zeros((B, L), dtype=torch.bool, device=attention_mask.device)
+            for s, (st, n) in enumerate(zip(self.starts, self.lengths)):
+                mask[s, st:st + n] = True
+            mask = mask.to(dtype=attention_mask.dtype)
+        if position_ids is not None:
+            pos = torch.zeros((B, L), dtype=position_ids.dtype, device=position_ids.device)
+            for s, (st, n) in enumerate(zip(self.starts, self.lengths)):
+                pos[s, st:st + n] = torch.arange(0, n, dtype=pos.dtype, device=pos.device)
+        return labels, mask, pos
+
+
+_ONE_VIDEO_PER_SAMPLE = ("the memory path supports one video per sample: with several videos in a forward, exactly as many samples "
+                         "as videos hold an image token, one each (llava_arch.py:436: 'Now support only batch size of 1'; a second "
+                         "video fails the reference's patch-grid assert, :636)")
+
+
+def features_per_sample(video_of, tokens):
+    """The feature list `splice_into_text` indexes: it advances its feature index over text-only samples too (llava_arch.py:
+    766-772, where the reference keeps a dummy feature per such sample), so the list has one entry per SAMPLE - the sample's
+    video block, or None where nothing is read."""
+    return [tokens[v] if v >= 0 else None for v in video_of]
+
+
+def run_video_groups(model, videos, mem_prompt, frame_prompt, image_newline, with_frames=True, layout="one_token",
+                     sizes=ROW_BATCH_SIZES, train=False, out=None, dst_rows=None, single=None):
+    """The memory path for several videos on the current stream - the ONE place that groups videos into row batches.
+    `videos`: (pooled frame tokens [T, P, D], original frame indices [T] on the host) per video.  Videos with the same sampled
+    frame count, dtype and device form a group (they share chunk bounds and fine-frame indices); `plan_row_batches` cuts it into
+    row batches, each stepped by `recurrent_memory_transformer.row_batcher(size)` with per-video frame indices; the rest run as
+    single videos on the model's own engine (`single(frames, idx, out)` -> tokens, default `video_memory_tokens`).
+      out is None   -> returns the token blocks [rows_v, D] in input order (`train`: under autograd, through
+                       video_memory_tokens_batched_train / the autograd path of video_memory_tokens)
+      out, dst_rows -> inference: video v's block is written at row dst_rows[v] of the contiguous [out_rows, D] buffer `out`:
+                       one emit per row batch (mavlm_fuse_emit_layout_batch_to), the `out=` slice for a single; returns None."""
+    rm = model.recurrent_memory_transformer
+    batches, singles = plan_row_batches([(v[0].shape[0], v[0].dtype, str(v[0].device)) for v in videos], sizes)
+    if single is None:
+        def single(frames, idx, o):
+            return video_memory_tokens(model, frames, idx, mem_prompt, frame_prompt, image_newline, with_frames, out=o,
+                                       layout=layout)[0]
+    tokens = [None] * len(videos)
+    for grp in batches:
+        bp = rm.row_batcher(len(grp))
+        frames, idxs = [videos[i][0] for i in grp], [videos[i][1] for i in grp]
+        if train:
+            toks = video_memory_tokens_batched_train(model, bp, frames, idxs, mem_prompt, frame_prompt, image_newline,
+                                                     with_frames, layout=layout)[0]
+        elif out is not None:
+            video_memory_tokens_batched(model, bp, frames, idxs, mem_prompt, frame_prompt, image_newline, with_frames, out=out,
+                                        layout=layout, dst_rows=[dst_rows[i] for i in grp])
+            continue
+        else:
+            toks = video_memory_tokens_batched(model, bp, frames, idxs, mem_prompt, frame_prompt, image_newline, with_frames,
+                                               layout=layout)[0]
+        for j, i in enumerate(grp):
+            tokens[i] = toks[j]
+    for i in singles:
+        frames, idx = videos[i]
+        if out is not None:
+            rows = video_token_rows(frames.shape[0], rm.num_memory_tokens, rm.patch_size, with_frames,
+                                    cache_cap=getattr(rm.config, "cache_cap", 10), n_mem_prompt=mem_prompt.shape[0],
+                                    n_frame_prompt=frame_prompt.shape[0], layout=layout)
+            single(frames, idx, out[dst_rows[i]:dst_rows[i] + rows])
+        else:
+            tokens[i] = single(frames, idx, None)
+    return None if out is not None else tokens
 
 
 def _tail_wants_grad(model, *tensors) -> bool:
@@ -724,8 +922,8 @@ class LlavaMetaForCausalLM:
             raise IndexError("list index out of range (no video among `images`: the reference's memory branch skips "
                              "non-video entries, llava_arch.py:487-490, and then indexes an empty feature list, :730)")
         if len(vids) != 1:
-            raise NotImplementedError("the memory path supports one video per forward (llava_arch.py:436: 'Now support "
-                                      "only batch size of 1'; a second video fails the reference's patch-grid assert, :636)")
+            return self._prepare_videos(model, [images[i] for i in vids], input_ids, position_ids, attention_mask,
+                                        past_key_values, labels)
         # non-video entries beside the video are encoded and then DROPPED by the reference (:487-490, 556): dropped here too
         images = [images[vids[0]]]
         layout = token_layout(self.config)                                                      # :562-634
@@ -752,6 +950,64 @@ class LlavaMetaForCausalLM:
             return direct
         tokens = self._video_tokens(model, pooled, idx_cpu, mem_prompt, frame_prompt, not drop, layout=layout)
         return splice_into_text(self, model, [tokens], input_ids, position_ids, attention_mask, past_key_values, labels)
+
+    # -- several videos per forward: one per sample, equal lengths stepped together as row batches ------------------------
+    row_batch_sizes = ROW_BATCH_SIZES        # sizes a group of equal-length videos is cut into (plan_row_batches); overridable
+
+    def _prepare_videos(self, model, videos, input_ids, position_ids, attention_mask, past_key_values, labels):
+        """`prepare_inputs_labels_for_multimodal` for V >= 2 videos: exactly V samples hold an image token, one each, and the
+        k-th of them takes the k-th video; the other samples are text only.  The result is what padding the single-sample
+        calls together gives (`splice_into_text`).  Videos of equal sampled length step together (`run_video_groups`); without a
+        gradient consumer every block is emitted straight into the padded buffer; the hipGraph cache steps aside."""
+        mask = torch.ones_like(input_ids, dtype=torch.bool) if attention_mask is None else attention_mask.bool()
+        ids_list = [i[m] for i, m in zip(input_ids, mask)]
+        ids_host = [i.tolist() for i in ids_list]
+        per_sample = [sum(t == IMAGE_TOKEN_INDEX for t in ids) for ids in ids_host]
+        if any(c > 1 for c in per_sample) or sum(per_sample) != len(videos):
+            raise NotImplementedError(_ONE_VIDEO_PER_SAMPLE)                 # (before anything is encoded)
+        layout = token_layout(self.config)                                                      # :562-634
+        newline = getattr(model, "image_newline", None)
+        _require_newline(newline, layout)
+        vids = []
+        for video in videos:                                   # per video, as the single-video branch does
+            idx_cpu = sample_frame_indices(video.shape[0])                                      # :437-451
+            pooled = self.get_2dPool(self.encode_images(video[idx_cpu.to(video.device)]))       # :457-481,495
+            vids.append((pooled, idx_cpu))
+        dev, dt, D = vids[0][0].device, vids[0][0].dtype, vids[0][0].shape[-1]
+        mem_prompt = model.embed_tokens(torch.tensor([MEMORY_PROMPT_IDS], device=dev)).squeeze(0)   # :708-709
+        frame_prompt = model.embed_tokens(torch.tensor([FRAME_PROMPT_IDS], device=dev)).squeeze(0)  # :714-715
+        # :719-720 - ONE draw per forward (one broadcast with a process group), applied to every video of the forward
+        drop = self.get_synced_dropout_decision(prob=0.5) and bool(getattr(self, "training", False)) and \
+            bool(getattr(self.config, "dropout_frames", False))
+        rm = model.recurrent_memory_transformer
+        rows = [video_token_rows(p.shape[0], rm.num_memory_tokens, rm.patch_size, not drop,
+                                 cache_cap=getattr(rm.config, "cache_cap", 10), layout=layout) for p, _ in vids]
+        plan = VideoPlacement(ids_host, rows, getattr(self.config, "tokenizer_padding_side", "right") == "left",
+                              getattr(self.config, "tokenizer_model_max_length", None))
+        train = path_wants_grad(model, mem_prompt, frame_prompt, newline)
+        if train or plan.general or not vids[0][0].is_cuda or any(p.device != dev or p.dtype != dt for p, _ in vids):
+            tokens = run_video_groups(model, vids, mem_prompt, frame_prompt, newline, not drop, layout, self.row_batch_sizes,
+                                      train=train)
+            return splice_into_text(self, model, features_per_sample(plan.video_of, tokens), input_ids, position_ids,
+                                    attention_mask, past_key_values, labels)
+        # in place: the padded buffer once, text rows from embed_tokens, padding zeroed, every block emitted where it belongs
+        B, L = len(ids_list), plan.Lmax
+        emb = torch.empty((B, L, D), device=dev, dtype=dt)
+        for s, lo, hi in plan.padding:
+            emb[s, lo:hi].zero_()
+        text = model.embed_tokens(torch.cat([ids_list[s][lo:hi] for s, lo, hi, _ in plan.segments])) if plan.segments else None
+        at = 0
+        for s, lo, hi, row in plan.segments:
+            emb[s, row:row + hi - lo] = text[at:at + hi - lo].to(dt)
+            at += hi - lo
+        with torch.no_grad():
+            run_video_groups(model, vids, mem_prompt, frame_prompt, newline, not drop, layout, self.row_batch_sizes,
+                             out=emb.view(B * L, D), dst_rows=plan.dst_row)
+        if text is not None and text.dtype != dt:
+            emb = emb.to(text.dtype)
+        lab_list = None if labels is None else [l[m] for l, m in zip(labels, mask)]
+        out_labels, out_mask, out_pos = plan.labels_mask_positions(lab_list, attention_mask, position_ids)
+        return None, _pos_skipping(self, out_pos, emb), out_mask, past_key_values, emb, out_labels
 
     # -- hipGraph replay for repeated video shapes (round 4) -------------------------------------------------------------
     def enable_memory_graphs(self, capacity: int = 4):

@@ -497,6 +497,7 @@ class TransformerProjector(nn.Module):
         """Give the engine the Memory-Fuser MLP and the token-type embedding (llava_arch.py:132-136,150) so that
         mavlm_fuse_emit can run fuser + type add + concat in one sequence."""
         self._fuser_refs = (memory_fuser, token_type_embedding)
+        self._row_batchers = {}
         if self._engine is not None:
             self._engine.version = None
 
@@ -507,8 +508,20 @@ class TransformerProjector(nn.Module):
         return tuple((p._version, p.data_ptr()) for p in ps)
 
     def refresh_weights(self):
+        self._row_batchers = {}
         if self._engine is not None:
             self._engine.version = None
+
+    def row_batcher(self, batch: int) -> "BatchedProjector":
+        """The `BatchedProjector` of `batch` videos over this module's parameters that the model entry point steps its row
+        batches with (llava_arch.run_video_groups): created on first use, kept beside the engine and dropped where the engine
+        is dropped (`_apply` that moves or casts the parameters, `refresh_weights`, `bind_fuser`).  One engine (rings,
+        workspace) per batch size in use."""
+        cache = self.__dict__.setdefault("_row_batchers", {})
+        bp = cache.get(int(batch))
+        if bp is None:
+            bp = cache[int(batch)] = BatchedProjector(self, int(batch), fused_ln_never=self._fused_ln_never)
+        return bp
 
     def engine(self, device, dtype, frames=None) -> _Engine:
         need = max(int(getattr(self.config, "max_chunk_frames", 32)), int(frames or 0))
@@ -536,6 +549,8 @@ class TransformerProjector(nn.Module):
             self._engine = None           # also ends a video in progress: its FIFO lived in the old engine
             self._memory_cache = []
             self._evo_kv = []
+        if before != after:
+            self._row_batchers = {}
         return out
 
     _fused_ln_never = False       # replicas of a pool with more than LN_MAX_STREAMS streams: GEMM + row LayerNorm kernels only
@@ -548,6 +563,7 @@ class TransformerProjector(nn.Module):
         import copy
         r = copy.copy(self)                    # shallow: _parameters / _modules dicts are shared
         r._engine = None
+        r._row_batchers = {}
         r._memory_cache = []
         r._evo_kv = []
         r.frame_attn_scores = []
