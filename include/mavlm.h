@@ -517,6 +517,17 @@ int mavlm_set_attention_wide_groups(int32_t groups);
  * writer per entry), take the tile-entry form as well (64-key tiles; round 4); 2 = diagnostics: the tile-entry form wherever it is
  * supported.  Same values up to fp32 summation order; the memory never depends on the mode. */
 int mavlm_set_frame_score_mode(int32_t mode);
+/* the per-(row, frame) form of the fused frame scores on the 8-wave stream-K plan at up to 32 frames per chunk: 1 (default) = a
+ * whole unit keeps its (a, m) entries in the workgroup's LDS (64 KiB of K / V ring + 66 KiB of entries) instead of writing
+ * them to the workspace and reading them back; the pieces of a cut unit copy theirs to the workspace once, after their key loop.
+ * 0 = every entry goes through the workspace.  Same values in the same order of additions: same bits (process-wide). */
+int mavlm_set_frame_entries_lds(int32_t on);
+/* first step of a video, first formation layer: the queries are a projection of the packed initial memory (mavlm_weights.mem0),
+ * which only mavlm_bind_weights replaces.  1 (default) = project it once per weight binding into a region of the workspace
+ * behind the regions mavlm_workspace_layout reports, and let every later first step read it (a first step that is being
+ * captured before any eager one projects inside the capture, as with 0).  0 = project at every first step.  Same GEMM,
+ * same bits.  Weights or an initial memory updated IN PLACE must be bound again (mavlm_bind_weights), as for mem0 itself. */
+int mavlm_set_cache_initial_q(int32_t on);
 /* dense + bias + residual + LayerNorm where the GEMM splits its contraction (small grids, K >= 2048 - the 4D -> D projection at few
  * memory tokens): 1 (default) = the fp32 planes go straight into ONE reduce + LayerNorm kernel (round 4), 0 = reduction pass, fp32
  * dense output, LayerNorm kernel.  Same arithmetic in the same order: same bits. */

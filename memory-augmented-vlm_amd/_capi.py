@@ -143,6 +143,8 @@ SIGNATURES = {
     "mavlm_set_attention_colsum_wgs": (C.c_int, [i32]),
     "mavlm_set_attention_wide_groups": (C.c_int, [i32]),
     "mavlm_set_frame_score_mode": (C.c_int, [i32]),
+    "mavlm_set_frame_entries_lds": (C.c_int, [i32]),
+    "mavlm_set_cache_initial_q": (C.c_int, [i32]),
     "mavlm_set_splitk_layernorm": (C.c_int, [i32]),
     "mavlm_set_gemm_short_splits": (C.c_int, [i32]),
     "mavlm_frame_scores_fused": (C.c_int, [i32, i32, i32, i32]),

@@ -21,6 +21,13 @@ namespace {
 constexpr int HD3 = 128, KT3 = 64;
 constexpr int TILE3 = KT3 * HD3 * 2;          // 16 KiB
 constexpr int ATTN3_LDS = 4 * TILE3;          // K0 K1 V0 V1
+// FR = 3 (frame entries in LDS): behind the K / V ring every wave owns [frame][row] x 8 bytes for its 32 rows and up to
+// FR3_FN frames.  Frame stride 32 * 8 + 8 bytes (66 dwords): a flush (32 rows of one frame, rows fastest) and the unit
+// epilogue's read (lane j = frame j of one row: banks 2 j, 2 j + 1) are both free of bank conflicts.
+constexpr int FR3_FN = 32;
+constexpr int FR3_FSTRIDE = 32 * 8 + 8;
+constexpr int FR3_WAVE = FR3_FN * FR3_FSTRIDE;                // 8 448 bytes per wave
+constexpr int ATTN3_LDS_FR3 = ATTN3_LDS + 8 * FR3_WAVE;       // 130 KiB of the CU's 160 (one 8-wave workgroup per CU)
 constexpr float RESCALE3_LOG2 = 8.0f;         // same deferred-rescale rule as attn_fwd_kernel (mirrored by the oracle)
 // LDS read-ahead, in MFMA steps, of the K fragments (phase A) and of the transposed V fragments (phase B).  One MFMA
 // step is 32-64 clocks of matrix pipe, an LDS read under load returns after 100-200: with a read-ahead of ONE step every
@@ -130,6 +137,10 @@ __host__ __device__ __forceinline__ int attn3_unit_of_level(const attn3_sk_plan&
 // row's final log-sum-exp - turns the entries of the cut units into partial frame sums in the same [unit][wave] layout.
 // An entry has exactly one writer: rows past R (clamped duplicates of row R-1) store to an offset behind the buffer
 // descriptor's end, which the hardware drops.
+// FR = 3 (8 waves, at most FR3_FN frames; mavlm_set_frame_entries_lds): the same values in the same order, but a wave keeps
+// the entries of its 32 rows in LDS behind the K / V ring - a whole unit never touches the scratch (no 8-byte store per row
+// and boundary, no 64 loads per lane at the end, no descriptor and entry offset held through the tile loop); a piece of a
+// cut unit copies its entries to the slots above once, after its key loop, for attn_combine_sk_kernel.
 //
 // Row batch (HB < H): the launch serves B = H / HB independent videos.  "Head" index h = b HB + hv: queries / outputs of
 // video b are the rows [b R, (b+1) R) of Q / O, its keys start kv_bs elements after video b-1's; lse2 is [B HB, R].
@@ -301,7 +312,11 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
   int f_cur = 0, f_end = FP;
   __amdgpu_buffer_rsrc_t frs;
   int f_voff = 0;
-  if constexpr (FR != 0) {
+  if constexpr (FR == 3) {
+    // the entries stay in LDS (see FR3_* below): no descriptor, no entry offset held through the tile loop
+    f_cur = (t_lo * KT3) / FP;
+    f_end = (f_cur + 1) * FP - t_lo * KT3;
+  } else if constexpr (FR != 0) {
     const uintptr_t fa = (uintptr_t)fscr;
     const uint32_t flo = __builtin_amdgcn_readfirstlane((uint32_t)fa);          // (uint32_t: readfirstlane returns int - no
     const uint32_t fhi = __builtin_amdgcn_readfirstlane((uint32_t)(fa >> 32));  //  sign extension into the high word)
@@ -321,6 +336,18 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
     f_cur = (t_lo * KT3) / FP;
     f_end = (f_cur + 1) * FP - t_lo * KT3;
   }
+  // FR = 3: entry (a, m) of this lane's row for frame f -> the wave's own LDS region (the address is rebuilt at every flush:
+  // nothing of it stays live through the tile loop).  LDS operations of a wave retire in order, and this write is OLDER than
+  // every K / V fragment read of the next tile: the hand-counted `lgkmcnt(n)` waits there, which leave only the n YOUNGEST
+  // operations outstanding, still cover the reads they are meant for.
+  // (the entry crosses the asm boundary as ONE 64-bit scalar, here and at both reads: with a u32x2 operand on a ds_read_b64
+  //  hipcc took element 0 for both halves)
+  [[maybe_unused]] auto fr3_put = [&](u32x2 e, int f) {
+    const unsigned a = (unsigned)(uintptr_t)(MAVLM_LDS char*)smem + (unsigned)(ATTN3_LDS + wave * FR3_WAVE + f * FR3_FSTRIDE) +
+                       8u * (unsigned)r;
+    const unsigned long long e64 = (unsigned long long)e[0] | ((unsigned long long)e[1] << 32);
+    asm volatile("ds_write_b64 %0, %1" ::"v"(a), "v"(e64) : "memory");
+  };
 
   // S(t) = K(t).Q^T into st[P] (no overlap; used for tile 0 only)
   auto qk_plain = [&](auto par, int slot) {
@@ -574,7 +601,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
         __builtin_amdgcn_raw_buffer_store_b64(e, frs, f_voff, t * R * 8, 0);
       }
     }
-    if constexpr (FR == 1) {
+    if constexpr (FR == 1 || FR == 3) {
       const int k_end = (t + 1) * KT3;
       if (f_end <= k_end) {                                   // the current frame ends inside (or at the end of) this tile
         flushed = true;
@@ -604,7 +631,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
           u32x2 e;
           e[0] = __builtin_bit_cast(unsigned, a_done);
           e[1] = __builtin_bit_cast(unsigned, m_run);
-          __builtin_amdgcn_raw_buffer_store_b64(e, frs, f_voff, f_cur * 8, 0);
+          if constexpr (FR == 3) fr3_put(e, f_cur);
+          else __builtin_amdgcn_raw_buffer_store_b64(e, frs, f_voff, f_cur * 8, 0);
         }
         a_cur = psum - plo;
         f_cur += 1;
@@ -624,7 +652,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
         const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
         m_run = m_new;
         l_run *= alpha;
-        if constexpr (FR == 1) a_cur *= alpha;
+        if constexpr (FR == 1 || FR == 3) a_cur *= alpha;
 #pragma unroll
         for (int d = 0; d < 4; ++d)
 #pragma unroll
@@ -634,7 +662,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
     // this wave's DMAs of K(t+2), V(t+1) have landed.  A frame entry stored in this tile is the YOUNGEST vector-memory
     // operation (the DMAs were issued in phase A) and retires last: leaving it in flight keeps its ~1 000-clock round trip
     // off the critical path of the barrier (waiting for it cost ~20 us per launch).
-    if (FR != 0 && flushed) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+    // (FR = 3: its entry went to LDS - no vector-memory operation of its own, the tile ends as in the plain kernel)
+    if (FR != 0 && FR != 3 && flushed) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -648,7 +677,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
   }
   if (t < nt) iteration(IC<0>{}, t);
 
-  if constexpr (FR == 1) {
+  if constexpr (FR == 1 || FR == 3) {
     // a piece that ends inside a frame: the mass of that frame's keys seen so far is still in a_cur (whole units end on a
     // frame boundary: S % FP == 0, the last flush happened in the loop and the next frame starts at key S)
     if (f_end - FP < S) {
@@ -657,7 +686,35 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
         u32x2 e;
         e[0] = __builtin_bit_cast(unsigned, a_done);
         e[1] = __builtin_bit_cast(unsigned, m_run);
-        __builtin_amdgcn_raw_buffer_store_b64(e, frs, f_voff, f_cur * 8, 0);
+        if constexpr (FR == 3) fr3_put(e, f_cur);
+        else __builtin_amdgcn_raw_buffer_store_b64(e, frs, f_voff, f_cur * 8, 0);
+      }
+      if constexpr (FR == 3) f_cur += 1;                      // (f_cur = one past the last frame this segment has an entry for)
+    }
+  }
+  if constexpr (FR == 3) {
+    if (out_kind == 2) {
+      // Cut piece: its entries go from LDS to the global scratch, into the slots f + piece that FR = 1 stores to during its
+      // key loop (attn_combine_sk_kernel reads them unchanged; one writer per entry).  Every lane copies what it wrote itself.
+      // Rows past R store to the offset behind the descriptor's end, which the hardware drops.  The descriptor and the
+      // offsets are built here, outside the tile loop.
+      const uintptr_t fa = (uintptr_t)fscr;
+      const uint32_t flo = __builtin_amdgcn_readfirstlane((uint32_t)fa);
+      const uint32_t fhi = __builtin_amdgcn_readfirstlane((uint32_t)(fa >> 32));
+      const uint32_t fbytes = __builtin_amdgcn_readfirstlane((uint32_t)H * (uint32_t)R * (uint32_t)FNE * 8u);
+      const __amdgpu_buffer_rsrc_t frs3 = __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)fhi << 32) | flo), 0, fbytes, 0x00020000);
+      int rz = r;
+      asm volatile("" : "+v"(rz));                             // (computed here, not hoisted out of the segment loop)
+      const int voff = q0 + rz < R ? ((h * R + q0 + rz) * FNE + sk_piece) * 8 : 0x7ffffff0;
+      const unsigned la = (unsigned)(uintptr_t)(MAVLM_LDS char*)smem + (unsigned)(ATTN3_LDS + wave * FR3_WAVE) + 8u * (unsigned)rz;
+      const int f_first = (t_lo * KT3) / FP;
+      for (int f = f_first; f < f_cur; ++f) {
+        unsigned long long e64;
+        asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(e64) : "v"(la + (unsigned)(f * FR3_FSTRIDE)) : "memory");
+        u32x2 e;
+        e[0] = (unsigned)e64;
+        e[1] = (unsigned)(e64 >> 32);
+        if (hh == 0) __builtin_amdgcn_raw_buffer_store_b64(e, frs3, voff, f * 8, 0);
       }
     }
   }
@@ -665,35 +722,39 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
   // ---- epilogue: O[q][h*128 + 32db + 8g + 4hh + 0..3] = O^T / l
   const float l_tot = xhalf_sum(l_run);
   const float inv = 1.0f / l_tot;
-  const int q = q0 + r;
+  // FR = 3: the lane's row and key half are made opaque here, so that the per-lane output addresses below are computed where
+  // they are used - hoisted out of the segment loop they sat in registers (or spill slots) through every tile loop
+  int r_e = r, hh_e = hh;
+  if constexpr (FR == 3) asm volatile("" : "+v"(r_e), "+v"(hh_e));
+  const int q = q0 + r_e;
   if (out_kind == 2) {                                        // stream-K partial: [slot][128 rows][128] + [slot][128]
-    float* pp = Opart + ((size_t)sk_slot * QB + wave * 32 + r) * HD3 + 4 * hh;
+    float* pp = Opart + ((size_t)sk_slot * QB + wave * 32 + r_e) * HD3 + 4 * hh_e;
 #pragma unroll
     for (int db = 0; db < 4; ++db)
 #pragma unroll
       for (int g = 0; g < 4; ++g)
         *(f32x4*)(pp + 32 * db + 8 * g) = f32x4{ot[db][4 * g] * inv, ot[db][4 * g + 1] * inv, ot[db][4 * g + 2] * inv,
                                                 ot[db][4 * g + 3] * inv};
-    if (hh == 0) lse_part[(size_t)sk_slot * QB + wave * 32 + r] = m_run * c + log2f(l_tot);
+    if (hh_e == 0) lse_part[(size_t)sk_slot * QB + wave * 32 + r_e] = m_run * c + log2f(l_tot);
   } else if (q < R) {
     if (out_kind == 1) {
-      float* pp = Opart + ((size_t)split * R + q) * (H * HD3) + h * HD3 + 4 * hh;
+      float* pp = Opart + ((size_t)split * R + q) * (H * HD3) + h * HD3 + 4 * hh_e;
 #pragma unroll
       for (int db = 0; db < 4; ++db)
 #pragma unroll
         for (int g = 0; g < 4; ++g)
           *(f32x4*)(pp + 32 * db + 8 * g) = f32x4{ot[db][4 * g] * inv, ot[db][4 * g + 1] * inv, ot[db][4 * g + 2] * inv,
                                                   ot[db][4 * g + 3] * inv};
-      if (hh == 0) lse_part[((size_t)split * H + h) * R + q] = m_run * c + log2f(l_tot);
+      if (hh_e == 0) lse_part[((size_t)split * H + h) * R + q] = m_run * c + log2f(l_tot);
     } else {
-      uint16_t* op = O + ((size_t)hb * R + q) * ldo + hv * HD3 + 4 * hh;
+      uint16_t* op = O + ((size_t)hb * R + q) * ldo + hv * HD3 + 4 * hh_e;
 #pragma unroll
       for (int db = 0; db < 4; ++db)
 #pragma unroll
         for (int g = 0; g < 4; ++g)
           *(u32x2*)(op + 32 * db + 8 * g) = pack4<T>(ot[db][4 * g] * inv, ot[db][4 * g + 1] * inv,
                                                      ot[db][4 * g + 2] * inv, ot[db][4 * g + 3] * inv);
-      if (lse2 != nullptr && hh == 0) lse2[(size_t)h * R + q] = m_run * c + log2f(l_tot);
+      if (lse2 != nullptr && hh_e == 0) lse2[(size_t)h * R + q] = m_run * c + log2f(l_tot);
     }
   }
   if (FR == 1 && out_kind == 0) {                             // whole unit: the row's final log-sum-exp is known here
@@ -723,6 +784,42 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
       fsum += ok ? ea[i] * __builtin_amdgcn_exp2f(em[i] * c - lse_i) : 0.f;
     }
     if (lane < FN) fout[((size_t)(h * nqb + qblk) * NW + wave) * FN + lane] = fsum;
+  }
+  if (FR == 3 && out_kind == 0) {                             // whole unit, entries in LDS: same values, same order of additions
+    // Lane j takes frame j (FN <= 32; the lanes behind it repeat frame FN - 1 and store nothing) and reads the entries of the
+    // wave's 32 rows for it: all 32 reads are issued before the first use.  The region is this wave's own and LDS operations
+    // retire in order, so one lgkmcnt(0) - no barrier - makes every entry written in the tile loop visible.
+    const float my_lse = m_run * c + log2f(l_tot);            // lane (r, hh): query q0 + r
+    float fsum = 0.f;
+    int lz = lane;
+    asm volatile("" : "+v"(lz));                               // (as r_e above)
+    const int fj = lz < FN ? lz : FN - 1;
+    const unsigned la = (unsigned)(uintptr_t)(MAVLM_LDS char*)smem + (unsigned)(ATTN3_LDS + wave * FR3_WAVE + fj * FR3_FSTRIDE);
+    unsigned long long en[32];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    auto eread = [&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      unsigned long long v;
+      asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(la), "i"(8 * i) : "memory");
+      en[i] = v;
+    };
+    eread(IC<0>{}); eread(IC<1>{}); eread(IC<2>{}); eread(IC<3>{}); eread(IC<4>{}); eread(IC<5>{}); eread(IC<6>{}); eread(IC<7>{});
+    eread(IC<8>{}); eread(IC<9>{}); eread(IC<10>{}); eread(IC<11>{}); eread(IC<12>{}); eread(IC<13>{}); eread(IC<14>{});
+    eread(IC<15>{}); eread(IC<16>{}); eread(IC<17>{}); eread(IC<18>{}); eread(IC<19>{}); eread(IC<20>{}); eread(IC<21>{});
+    eread(IC<22>{}); eread(IC<23>{}); eread(IC<24>{}); eread(IC<25>{}); eread(IC<26>{}); eread(IC<27>{}); eread(IC<28>{});
+    eread(IC<29>{}); eread(IC<30>{}); eread(IC<31>{});
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 32; ++i) asm volatile("" : "+v"(en[i]));      // (uses stay behind the wait)
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+      const float lse_i = __shfl(my_lse, i);                  // lanes i and i + 32 hold the same row
+      const bool ok = q0 + i < R && lz < FN;
+      const float ea = __builtin_bit_cast(float, (unsigned)en[i]), em = __builtin_bit_cast(float, (unsigned)(en[i] >> 32));
+      fsum += ok ? ea * __builtin_amdgcn_exp2f(em * c - lse_i) : 0.f;
+    }
+    if (lz < FN) fout[((size_t)(h * nqb + qblk) * NW + wave) * FN + lz] = fsum;
   }
   }   // segment loop (every tile iteration ends with a barrier: the LDS slots are free for the next segment's prologue)
 }
@@ -1026,14 +1123,15 @@ template <typename T, int NW, int FR>
 hipError_t attn3_launch(const mavlm_attn_args& a, const attn3_launch_args& la, hipStream_t s) {
   auto kern = attn_fwd3_kernel<T, NW, FR>;
   static mavlm_per_device_once once;
-  hipError_t e = once.dyn_lds((const void*)kern, ATTN3_LDS);
+  constexpr int LDS = FR == 3 ? ATTN3_LDS_FR3 : ATTN3_LDS;
+  hipError_t e = once.dyn_lds((const void*)kern, LDS);
   if (e != hipSuccess) return e;
   const int FN = FR ? a.S / a.frame_keys : 0;
   {  // (bench.py's instrumented pass: the main kernel and the merge are bracketed separately, so the main kernel's average
      // is directly comparable with its line in a rocprofv3 summary)
     mavlm_prof_scope prof(FR ? MAVLM_K_ATTN_FRAMES : MAVLM_K_ATTN, 4.0 * a.R * (double)a.S * a.H * HD3,
                           2.0 * HD3 * a.H * (2.0 * a.R + 2.0 * a.S), s);
-    hipLaunchKernelGGL(kern, la.grid, dim3(64 * NW), ATTN3_LDS, s, (const uint16_t*)a.Q, a.ldq, (const uint16_t*)a.K, a.ldk,
+    hipLaunchKernelGGL(kern, la.grid, dim3(64 * NW), LDS, s, (const uint16_t*)a.Q, a.ldq, (const uint16_t*)a.K, a.ldk,
                        (const uint16_t*)a.V, a.ldv, (uint16_t*)a.O, a.ldo, a.lse2, a.R, a.S, a.H, la.c, la.opart, la.lpart,
                        la.tps, la.plan, la.HB, (long long)a.kv_bstride, FR ? a.frame_scr : (float*)nullptr,
                        FR ? a.frame_out : (float*)nullptr, FR ? a.frame_keys : 0, FN, la.FNE);
@@ -1047,7 +1145,7 @@ hipError_t attn3_launch(const mavlm_attn_args& a, const attn3_launch_args& la, h
                         0.0, parts * 4.0 * (HD3 + 1), s);
   if (la.plan.wgs > 0 && la.cut_units > 0) {
     attn3_frames_args fa = {};
-    constexpr int FRM = FR == 1 ? 1 : 0;                      // (FR = 2: the tile entries need no merge)
+    constexpr int FRM = (FR == 1 || FR == 3) ? 1 : 0;         // (FR = 2: the tile entries need no merge; FR = 3 leaves FR = 1's entries)
     if (FRM) fa = attn3_frames_args{a.frame_scr, a.frame_out, a.frame_keys, FN, la.FNE, a.S, la.c};
     hipLaunchKernelGGL((attn_combine_sk_kernel<T, FRM>), dim3(la.cut_units * (la.plan.qb / 32)), dim3(256), 0, s, la.opart,
                        la.lpart, (uint16_t*)a.O, a.ldo, a.lse2, a.R, a.H, la.plan, la.plan.qb, la.HB, fa);
@@ -1064,6 +1162,7 @@ hipError_t attn3_launch(const mavlm_attn_args& a, const attn3_launch_args& la, h
 }
 }  // namespace
 
+int g_mavlm_frame_entries_lds = 1;  // mavlm_set_frame_entries_lds: FR = 3 where it applies (process-wide; it changes no bits)
 int g_mavlm_frame_score_mode = 1;   // mavlm_step: 1 = frame scores fused into the last layer's forward, 0 = column-sum pass
 
 // scores[b][f] = (1 / P) * sum of the partial frame sums of video b (rows [b rows, (b+1) rows) of fout), added in a fixed
@@ -1163,6 +1262,9 @@ static hipError_t attn3_dispatch(const mavlm_attn_args& a, int dtype, int frames
     return w8 ? attn3_launch<BF16, 8, 2>(a, la, s) : attn3_launch<BF16, 4, 2>(a, la, s);
   }
   if (frames) {
+    // the 8-wave stream-K plan at up to FR3_FN frames: the (a, m) entries of whole units stay in LDS (same bits as FR = 1)
+    if (w8 && g_mavlm_frame_entries_lds && a.S / a.frame_keys <= FR3_FN)
+      return h16 ? attn3_launch<F16, 8, 3>(a, la, s) : attn3_launch<BF16, 8, 3>(a, la, s);
     if (h16) return w8 ? attn3_launch<F16, 8, 1>(a, la, s) : attn3_launch<F16, 4, 1>(a, la, s);
     return w8 ? attn3_launch<BF16, 8, 1>(a, la, s) : attn3_launch<BF16, 4, 1>(a, la, s);
   }

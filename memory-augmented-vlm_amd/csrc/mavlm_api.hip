@@ -46,9 +46,16 @@ struct mavlm_ctx {
   int ln_wide = 0;     // ... and of its "rows of up to 4096 columns" test mode
   float* maps = nullptr;    // attention maps of every step (mavlm_bind_attention_maps): the caller's buffer, null = off
   bool lnx_clean = false;   // the exchange scratch of this workspace has been zero-filled since the last mavlm_bind_buffers
+  // Q of the first step's first formation layer, mem0 . Wq^T + bq: a function of the bound weights alone.  Projected once
+  // per binding into its own region (o_q0, behind every other region of the carve); cleared by mavlm_bind_weights (other
+  // weights) and mavlm_bind_buffers (another workspace)
+  size_t o_q0 = 0;
+  bool q0_valid = false;
+  const void* q_used = nullptr;   // the Q the last attn_block ran on (o_q, or o_q0): what the passes behind it read
 };
 
 int g_mavlm_fused_ln = 1;   // process-wide hook (mavlm_set_fused_layernorm); contexts snapshot it at mavlm_create
+int g_mavlm_cache_q0 = 1;   // the first step's first Q projection is made once per weight binding (mavlm_set_cache_initial_q)
 int g_mavlm_splitk_ln = 1;  // dense + LayerNorm over a split contraction: planes -> reduce + LayerNorm in one kernel (mavlm_set_splitk_layernorm)
 
 namespace {
@@ -259,6 +266,7 @@ void carve(mavlm_ctx* x) {
   x->o_stage = 0;
   x->stage_bytes = fuse_stage_bytes(c, x->fuse_mems, x->gsplit_floats);
   if (x->stage_bytes) { x->o_stage = o; o += al(x->stage_bytes); }
+  x->o_q0 = o; o += al(R * Dp * 2);       // (LAST: no other offset moves)
   x->total = o;
 }
 
@@ -346,13 +354,15 @@ int dense_ln(mavlm_ctx* x, hipStream_t s, const void* A, int lda, const void* W,
 // frame_rows (out): rows of the partial frame sums per video when `frames` (argument of the finish kernel)
 int attn_block(mavlm_ctx* x, hipStream_t s, const mavlm_attn_weights& aw, const void* xq, const void* K, int ldk,
                const void* V, int ldv, long long kv_bs, int S, void* out, float* lse2, int frames = 0,
-               int* frame_rows = nullptr) {
+               int* frame_rows = nullptr, const void* q_pre = nullptr) {
   const mavlm_config& c = x->cfg;
   const int B = nbatch(c), R1 = q_tokens(c) * c.patches, R = R1 * B, D = c.hidden, H = c.heads, dt = c.dtype,
             Dp = padded_width(c);
-  MAVLM_TRY(gemm_x(x, s, xq, D, aw.wq, D, aw.bq, ws(x, x->o_q), Dp, R, Dp, D, MAVLM_EPI_BIAS));
+  // q_pre: the projection of xq made earlier (the initial memory of a first step): no GEMM
+  if (!q_pre) MAVLM_TRY(gemm_x(x, s, xq, D, aw.wq, D, aw.bq, ws(x, x->o_q), Dp, R, Dp, D, MAVLM_EPI_BIAS));
+  x->q_used = q_pre ? q_pre : ws(x, x->o_q);
   mavlm_attn_args a;
-  a.Q = ws(x, x->o_q); a.ldq = Dp; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = ws(x, x->o_ctx); a.ldo = Dp;
+  a.Q = x->q_used; a.ldq = Dp; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = ws(x, x->o_ctx); a.ldo = Dp;
   a.lse2 = lse2; a.R = R1; a.S = S; a.H = H * B; a.nb = B; a.kv_bstride = kv_bs; a.scale = attn_scale(c);
   if (wide_heads(c)) {
     // wide heads (448: the OneVision-7B width): the row batch is the grid's z dimension, or - when its units exceed the 256
@@ -429,13 +439,13 @@ size_t maps_floats(const mavlm_config& c) {
   const size_t e = mavlm_group_mass_floats(Rq1, c.cache_cap * R1, H, P, R1) - mavlm_group_mass_out_floats(Rq1, c.cache_cap * R1, H, P, R1);
   return (size_t)nbatch(c) * maps_video_floats(c) + (f > e ? f : e);
 }
-// the pass behind one attention of the step: Q of the block sits in the workspace (o_q), lse2 in o_lse; one launch pair per video
+// the pass behind one attention of the step: Q of the block sits in the workspace (q_used), lse2 in o_lse; one launch pair per video
 int step_maps(mavlm_ctx* x, hipStream_t s, const char* K, int ldk, long long kv_bs, int S, int k_group, int k_rot, size_t out_off) {
   const mavlm_config& c = x->cfg;
   const int B = nbatch(c), Rq1 = q_tokens(c) * c.patches, H = c.heads, Dp = padded_width(c);
   for (int b = 0; b < B; ++b) {
     mavlm_group_mass_args g;
-    g.Q = ws(x, x->o_q) + (size_t)b * Rq1 * Dp * 2; g.ldq = Dp; g.K = K + (size_t)b * kv_bs * 2; g.ldk = ldk;
+    g.Q = (const char*)x->q_used + (size_t)b * Rq1 * Dp * 2; g.ldq = Dp; g.K = K + (size_t)b * kv_bs * 2; g.ldk = ldk;
     g.lse2 = (const float*)ws(x, x->o_lse) + (size_t)b * H * Rq1;
     g.out = x->maps + (size_t)b * maps_video_floats(c) + out_off;
     g.scratch = x->maps + (size_t)B * maps_video_floats(c);
@@ -533,8 +543,23 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
     const int fused_scores = want_scores ? step_frames_fused(x, S) : 0;
     float* lse = want_scores ? (float*)ws(x, x->o_lse) : maps_lse;     // (the fused form does not need it; kept for inspection)
     int frows = 0;
+    // First step, first layer: cur is the packed initial memory and Q = mem0 . Wq^T + bq depends on the bound weights alone -
+    // projected once per binding into o_q0.  A capture that starts before any eager first step keeps the GEMM inside the
+    // graph (into o_q, flag untouched): the graph stays self-contained.  A graph captured with the flag set reads o_q0, which
+    // goes stale exactly when the packed mem0 it also reads does.
+    const void* q_pre = nullptr;
+    if (l == 0 && x->steps == 0 && g_mavlm_cache_q0) {
+      if (!x->q0_valid) {
+        hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cst) == hipSuccess && cst == hipStreamCaptureStatusNone) {
+          MAVLM_TRY(gemm_x(x, s, cur, D, x->w.layer_attn[0].wq, D, x->w.layer_attn[0].bq, ws(x, x->o_q0), Dp, R, Dp, D, MAVLM_EPI_BIAS));
+          x->q0_valid = true;
+        }
+      }
+      if (x->q0_valid) q_pre = ws(x, x->o_q0);
+    }
     int rc = attn_block(x, s, x->w.layer_attn[l], cur, Kl, ldkv, Vl, ldkv, (long long)S * ldkv, S, ws(x, x->o_a), lse,
-                        fused_scores, &frows);
+                        fused_scores, &frows, q_pre);
     if (rc) return rc;
     if (x->maps) {        // [H, M, F] of layer l: query group = one memory token, key group = one frame
       rc = step_maps(x, s, Kl, ldkv, (long long)S * ldkv, S, c.patches, 0, (size_t)l * H * q_tokens(c) * F);
@@ -545,7 +570,7 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
     } else if (want_scores) {
       for (int b = 0; b < B; ++b) {          // (one pass per video: the column-sum kernels know nothing of the row batch)
         mavlm_colsum_args ca;
-        ca.Q = ws(x, x->o_q) + (size_t)b * Rq1 * Dp * 2; ca.ldq = Dp; ca.K = Kl + (size_t)b * S * ldkv * 2; ca.ldk = ldkv;
+        ca.Q = (const char*)x->q_used + (size_t)b * Rq1 * Dp * 2; ca.ldq = Dp; ca.K = Kl + (size_t)b * S * ldkv * 2; ca.ldk = ldkv;
         ca.lse2 = lse + (size_t)b * H * Rq1; ca.part = (float*)ws(x, x->o_part);
         ca.R = Rq1; ca.S = S; ca.H = H; ca.scale = attn_scale(c);
         int planes = 1;
@@ -658,6 +683,18 @@ int mavlm_set_gemm_short_splits(int32_t splits) {
   return 0;
 }
 
+int mavlm_set_frame_entries_lds(int32_t on) {
+  if (on != 0 && on != 1) return MAVLM_E_ARG;
+  g_mavlm_frame_entries_lds = on;
+  return 0;
+}
+
+int mavlm_set_cache_initial_q(int32_t on) {
+  if (on != 0 && on != 1) return MAVLM_E_ARG;
+  g_mavlm_cache_q0 = on;
+  return 0;
+}
+
 int mavlm_set_splitk_layernorm(int32_t on) {
   if (on != 0 && on != 1) return MAVLM_E_ARG;
   g_mavlm_splitk_ln = on;
@@ -761,6 +798,7 @@ int mavlm_bind_weights(mavlm_ctx* x, const mavlm_weights* w) {
       return MAVLM_E_ARG;
   }
   x->w = *w;
+  x->q0_valid = false;                          // (so is the projection of the previous initial memory)
   x->pre[0].seg = x->pre[1].seg = nullptr;      // K/V projected with the previous weights are not this context's any more
   x->has_w = true;
   return 0;
@@ -771,6 +809,7 @@ int mavlm_bind_buffers(mavlm_ctx* x, const mavlm_buffers* b) {
   if (b->workspace_bytes < x->total || ((uintptr_t)b->workspace & 255)) return MAVLM_E_ARG;
   x->b = *b;
   x->has_b = true;
+  x->q0_valid = false;             // ... and the cached first-step Q lived in the old one
   x->lnx_clean = false;            // a new workspace: its exchange scratch is zero-filled at the first step
   x->pre[0] = x->pre[1] = mavlm_ctx::pre_slot();     // (a prefetched projection lived in the old workspace)
   x->done_rec[0] = x->done_rec[1] = false;

@@ -134,6 +134,7 @@ hipError_t mavlm_launch_attention3_frames(const mavlm_attn_args& a, int dtype, h
 hipError_t mavlm_launch_frame_finish(const float* fout, int rows, int nb, int F, int P, void* out, int out_f32, int dtype,
                                      hipStream_t s);
 int mavlm_attention_frames_rows_per_video(const mavlm_attn_args& a);
+extern int g_mavlm_frame_entries_lds;  // 1 (default) = whole units of the 8-wave plan keep their frame entries in LDS (attention3.hip FR = 3)
 extern int g_mavlm_frame_score_mode;   // 1 (default) = fused into the last layer's forward, 0 = column-sum pass
 // split-KV plan for grids too small to fill the chip (attention3.hip): number of key splits (1 = none)
 int mavlm_attention_splits(int R, int S, int H, int* tiles_per_split);

@@ -19,8 +19,8 @@ def sub1(src, old, new):
 
 def make(src, v):
     if v == "nostore":
-        src = sub1(src, "          __builtin_amdgcn_raw_buffer_store_b64(e, frs, f_voff, f_cur * 8, 0);\n        }\n        a_cur = psum - plo;",
-                   "          asm volatile(\"\" :: \"v\"(e));\n        }\n        a_cur = psum - plo;")
+        src = sub1(src, "          else __builtin_amdgcn_raw_buffer_store_b64(e, frs, f_voff, f_cur * 8, 0);\n        }\n        a_cur = psum - plo;",
+                   "          else asm volatile(\"\" :: \"v\"(e));\n        }\n        a_cur = psum - plo;")
     if v == "nogroups":
         i = src.index("        float plo;\n        if (kofs <= 32) {                                     // boundary in block 0")
         j = src.index("        const float a_done = xhalf_sum(a_cur + plo);          // both key halves of the row")
@@ -55,7 +55,9 @@ def run_one():
     sys.path.insert(0, ROOT)
     import torch
     import memory_augmented_vlm_amd  # noqa: F401
+    from memory_augmented_vlm_amd import _capi as capi
     from memory_augmented_vlm_amd import _ops as ops
+    capi.lib().mavlm_set_frame_entries_lds(0)             # (the ablations are of the scratch form, FR = 1)
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from diag_vs_hipblaslt_util import timeit_pair
     H, R, S = 8, 12544, 6272
