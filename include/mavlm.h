@@ -161,6 +161,24 @@ int mavlm_step(mavlm_ctx* ctx, const void* seg, int32_t F, void* frame_scores, i
  * exact for every row-wise operator, the attention keeps each video on its own keys.  Not bit-identical to B single-video
  * contexts where the attention schedule differs (fp32 summation order of the cut units); same rounding points. */
 int mavlm_step_batch(mavlm_ctx* ctx, const void* const* segs, int32_t F, void* frame_scores, int32_t scores_f32, void* stream);
+/* Ragged row batch: the same step for a PREFIX of the videos of a row-batched context - videos 0 .. n_active-1 (the reference
+ * steps every video over its own chunks, llava_arch.py:436,534-537: a video with fewer chunks simply stops earlier).  All
+ * videos of a batch start together, ordered longest first, and n_active only ever shrinks: 1 <= n_active <= B
+ * (MAVLM_E_ARG otherwise), and not above the n_active of the previous step since mavlm_reset (MAVLM_E_STATE, nothing enqueued).
+ * segs = HOST array of n_active device pointers; frame_scores: null or [n_active, F].  mavlm_step_batch is this call with
+ * n_active = B.
+ * Launch contract, n_active >= 2: the launches of mavlm_step_batch on a context created with batch = n_active over the same
+ * ring contents - same GEMM shapes, tiles and split plans, same attention plan over the n_active * heads pairs, same
+ * frame-score form, same fused / two-kernel LayerNorm choice: the same bits.  n_active = 1 runs the row-batch rules at one
+ * video (never the split-KV attention, the evolution K/V projection through the row map without a split, no chunk K/V made
+ * ahead; the other GEMMs take the plan of their shape) - not the single-video context's schedule.  Only rows of active videos are written, in the new ring slot and in evo_kv_ring: the rows of a finished video stay,
+ * in every slot, as its own last steps left them.  The scratch whose size follows the video count is sized at mavlm_create for
+ * the largest need over 1 .. B videos, behind the regions a context stepped with n_active = B uses (none of those moves). */
+int mavlm_step_batch_active(mavlm_ctx* ctx, const void* const* segs, int32_t n_active, int32_t F, void* frame_scores,
+                            int32_t scores_f32, void* stream);
+/* steps video b of the context has taken since mavlm_reset (single video: b = 0).  mavlm_cache_len / mavlm_newest_slot /
+ * mavlm_steps count the context's steps, which are video 0's.  MAVLM_E_ARG: b outside 0 .. B-1. */
+int mavlm_video_steps(const mavlm_ctx* ctx, int32_t b);
 /* Attention maps of the steps (off by default).  While a buffer of mavlm_attention_maps_floats(cfg) floats is bound, every
  * mavlm_step / mavlm_step_batch runs the group-mass pass behind each attention of the step and writes, for video b of the row
  * batch, at maps + b * V with V = depth*H*M*max_chunk_frames + H*M*cache_cap  (M = mem_tokens, or q_tokens of a row shard):
@@ -247,6 +265,24 @@ int mavlm_fuse_emit_layout_batch_to(mavlm_ctx* ctx, const void* const* x_pe, con
                                     const void* mem_prompt, int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt,
                                     const void* newline, int32_t with_frames, int32_t layout, void* out, int64_t out_rows,
                                     const int64_t* dst_row, int64_t* rows, void* stream);
+/* The emit behind a ragged row batch (mavlm_step_batch_active; llava_arch.py:436,545-554 per video): videos 0 .. n_videos-1
+ * of the context hold different numbers of memories.  Video b has n_b = min(mavlm_video_steps(b), cache_cap) of them, oldest
+ * first; its oldest ring slot is 0 while it has not wrapped, else steps_b % cache_cap.  Its block
+ *   [mem_prompt ; layout(its n_b fused memories) ; frame_prompt ; layout(its fine frames)]
+ * of rows[b] = mavlm_layout_rows(cfg, n_b, n_fine, ...) rows is written at row dst_row[b] of `out` ([out_rows, D]).  x_pe, dst_row
+ * and rows are HOST arrays of n_videos entries (rows is written); fine_idx is a DEVICE array [n_videos, n_fine]: one index row
+ * per video (the videos sample their fine frames over their own lengths).  1 <= n_videos <= min(B, 16).
+ * The longest-first order makes the videos that hold a ring slot a prefix: per slot, the fuser GEMM pair runs over the rows of
+ * that prefix and writes through the row map and the per-video bases of mavlm_fuse_emit_layout_batch_to; consecutive slots
+ * that all B videos hold at consecutive places of their blocks still share one GEMM pair (up to the context's batch of cached
+ * memories per launch).  The fused rows are the ring's rows through the launches of mavlm_fuse_emit_layout_batch_to for that
+ * shape.  Checked on the host before anything is enqueued, MAVLM_E_ARG otherwise: every block inside `out`, the blocks
+ * pairwise disjoint by their own lengths, 16-byte alignment.  MAVLM_E_STATE: a single-video context, or a video without a
+ * step.  Rows of `out` outside the blocks are not touched. */
+int mavlm_fuse_emit_layout_ragged_to(mavlm_ctx* ctx, int32_t n_videos, const void* const* x_pe, const int64_t* fine_idx,
+                                     int32_t n_fine, const void* mem_prompt, int32_t n_mem_prompt, const void* frame_prompt,
+                                     int32_t n_frame_prompt, const void* newline, int32_t with_frames, int32_t layout, void* out,
+                                     int64_t out_rows, const int64_t* dst_row, int64_t* rows, void* stream);
 /* Host only: rows of the token block of a video with n_memories cached memories and n_fine fine frames in a layout - the
  * sequence length the concat of llava_arch.py:722-731 ends up with after :567-634.  <0: MAVLM_E_ARG (bad config / counts /
  * layout), MAVLM_E_SHAPE (_GRID: patches is not a square). */

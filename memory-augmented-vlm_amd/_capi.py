@@ -66,6 +66,8 @@ SIGNATURES = {
     "mavlm_pe_add": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "mavlm_step": (C.c_int, [vp, vp, i32, vp, i32, vp]),
     "mavlm_step_batch": (C.c_int, [vp, C.POINTER(vp), i32, vp, i32, vp]),
+    "mavlm_step_batch_active": (C.c_int, [vp, C.POINTER(vp), i32, i32, vp, i32, vp]),
+    "mavlm_video_steps": (C.c_int, [vp, i32]),
     "mavlm_batch": (C.c_int, [vp]),
     "mavlm_project_chunk": (C.c_int, [vp, vp, i32, vp]),
     "mavlm_project_chunk_ahead": (C.c_int, [vp, vp, i32, vp]),
@@ -78,6 +80,8 @@ SIGNATURES = {
                                                C.POINTER(C.c_int64), vp]),
     "mavlm_fuse_emit_layout_batch_to": (C.c_int, [vp, C.POINTER(vp), vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64,
                                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
+    "mavlm_fuse_emit_layout_ragged_to": (C.c_int, [vp, i32, C.POINTER(vp), vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64,
+                                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
     "mavlm_fuse_emit_layout": (C.c_int, [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64,
                                          C.POINTER(C.c_int64), vp]),
     "mavlm_layout_rows": (C.c_int64, [C.POINTER(Config), i32, i32, i32, i32, i32, i32]),

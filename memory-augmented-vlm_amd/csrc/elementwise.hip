@@ -279,12 +279,17 @@ __global__ __launch_bounds__(256) void row_add_kernel(const uint16_t* __restrict
 // of the `grid` / `frame` token layouts (llava_arch.py:330-357), written by copy_rows_kernel
 struct row_add_srcs { const uint16_t* p[16]; };
 // VB (an instantiation of its own): video b's output starts vb.off[b] elements into `out` instead of b * vstride
-template <typename T, bool GAP = false, bool VB = false>
+// SV (again its own; an empty argument otherwise): video b gathers through src + b * ss.v - an index row per video (ragged
+// row batches: the videos sample their fine frames over their own lengths); the shared indices are stride 0, SV = false
+template <bool SV> struct row_add_sstride {};
+template <> struct row_add_sstride<true> { long long v; };
+template <typename T, bool GAP = false, bool VB = false, bool SV = false>
 __global__ __launch_bounds__(256) void row_add_batch_kernel(row_add_srcs xs, const int64_t* __restrict__ src,
                                                             const uint16_t* __restrict__ table, uint16_t* __restrict__ out,
                                                             long long vstride, int T_, int P, int D, int gap,
-                                                            mavlm_vbase_arg<VB> vb) {
+                                                            mavlm_vbase_arg<VB> vb, row_add_sstride<SV> ss) {
   const uint16_t* __restrict__ x = xs.p[blockIdx.y];
+  if constexpr (SV) src += (size_t)blockIdx.y * ss.v;
   if constexpr (VB) out += (size_t)vb.off[blockIdx.y];
   else out += (size_t)blockIdx.y * vstride;
   const int dv = D >> 3;
@@ -467,10 +472,11 @@ hipError_t mavlm_launch_row_add(const void* x, const int64_t* src, const void* t
 
 hipError_t mavlm_launch_row_add_batch(const void* const* x, const int64_t* src, const void* table_row, void* out,
                                       long long vstride, int B, int T_, int P, int D, int dtype, hipStream_t s, int gap,
-                                      const long long* vbase) {
+                                      const long long* vbase, long long src_vstride) {
   if (T_ <= 0 || B <= 0) return hipSuccess;
   if (!x || !table_row || !out || P <= 0 || D <= 0 || (D & 7) || gap < 0) return hipErrorInvalidValue;
   if (vbase && B > MAVLM_VBASE_MAX) return hipErrorInvalidValue;
+  if (src_vstride != 0 && (src_vstride < 0 || !vbase || !src)) return hipErrorInvalidValue;
   const size_t total = (size_t)T_ * P * (D >> 3);
   mavlm_prof_scope prof(MAVLM_K_ROWADD, 0.0, 4.0 * B * T_ * (double)P * D, s);
   size_t blocks = (total + 255) / 256;
@@ -485,7 +491,19 @@ hipError_t mavlm_launch_row_add_batch(const void* const* x, const int64_t* src, 
     uint16_t* o = (uint16_t*)out + (size_t)b0 * vstride;
 #define RAB(TT, GG, VV, vb)                                                                                                \
   hipLaunchKernelGGL((row_add_batch_kernel<TT, GG, VV>), dim3((unsigned)blocks, (unsigned)nb), dim3(256), 0, s, xs, src, \
-                     (const uint16_t*)table_row, o, vstride, T_, P, D, gap, vb)
+                     (const uint16_t*)table_row, o, vstride, T_, P, D, gap, vb, row_add_sstride<false>{})
+#define RABS(TT, GG, vb)                                                                                                         \
+  hipLaunchKernelGGL((row_add_batch_kernel<TT, GG, true, true>), dim3((unsigned)blocks, (unsigned)nb), dim3(256), 0, s, xs, src, \
+                     (const uint16_t*)table_row, o, vstride, T_, P, D, gap, vb, row_add_sstride<true>{src_vstride})
+    if (vbase && src_vstride) {          // (an index row per video)
+      const mavlm_vbase_arg<true> vb = mavlm_vbase_pack(vbase, nb);
+      if (dtype == MAVLM_F16) {
+        if (gap > 0) RABS(F16, true, vb); else RABS(F16, false, vb);
+      } else {
+        if (gap > 0) RABS(BF16, true, vb); else RABS(BF16, false, vb);
+      }
+      continue;
+    }
     if (vbase) {          // (B <= 16: one pass of this loop)
       const mavlm_vbase_arg<true> vb = mavlm_vbase_pack(vbase, nb);
       if (dtype == MAVLM_F16) {
@@ -502,6 +520,7 @@ hipError_t mavlm_launch_row_add_batch(const void* const* x, const int64_t* src, 
       if (gap > 0) RAB(BF16, true, false, vb0); else RAB(BF16, false, false, vb0);
     }
 #undef RAB
+#undef RABS
   }
   return hipGetLastError();
 }

@@ -51,7 +51,21 @@ struct mavlm_ctx {
   // weights) and mavlm_bind_buffers (another workspace)
   size_t o_q0 = 0;
   bool q0_valid = false;
+  int q0_nb = 0;                  // videos whose rows the projection covers (a prefix of a larger one is valid: the rows of B
+                                  // copies of mem0), and whether it split its contraction (then only the same count reads it)
+  bool q0_split = false;
   const void* q_used = nullptr;   // the Q the last attn_block ran on (o_q, or o_q0): what the passes behind it read
+  // Ragged row batch (mavlm_step_batch_active): a step serves the first nb videos.  view[v] holds what the carve of a context
+  // created with batch = v decides by - a step over v videos takes the schedule of that context (v = 1: the row-batch rules at
+  // one video).  view[B] is this context's own carve.  Where a view needs more scratch than the region of the own carve, the
+  // steps with nb < B use a region of their own BEHIND o_q0 (o_x*: 0 = the own region covers every view).
+  struct nb_view { size_t gsplit_floats = 0, split_floats = 0, lnx_bytes = 0, fscr_floats = 0, fout_floats = 0; bool fscr = false, ftiles_ok = false; };
+  nb_view view[MAVLM_MAX_BATCH + 1];
+  int nb = 1;                     // videos of the step / emit launch in flight (B outside mavlm_step_batch_active)
+  size_t fscr_floats = 0, fout_floats = 0;
+  size_t o_xsplit = 0, o_xgsplit = 0, o_xfscr = 0, o_xfout = 0;
+  int n_active = 0;               // videos of the last step since mavlm_reset (0 = none yet)
+  int vsteps[MAVLM_MAX_BATCH] = {};   // steps of each video since mavlm_reset
 };
 
 int g_mavlm_fused_ln = 1;   // process-wide hook (mavlm_set_fused_layernorm); contexts snapshot it at mavlm_create
@@ -147,9 +161,13 @@ size_t fuse_stage_bytes(const mavlm_config& c, int fuse_mems, size_t gsplit_floa
   return rows_max * (size_t)c.hidden * 2;
 }
 
-void carve(mavlm_ctx* x) {
+// rb_one: the carve of ONE video under the row-batch rules (the nb = 1 view of a row-batched context): none of the single-video
+// context's extras - no second chunk K/V buffer, no split-KV partials (the GEMMs of a step keep the plan of their shape; the
+// evolution K/V projection goes through the row map, which never splits)
+void carve_core(mavlm_ctx* x, bool rb_one = false) {
   const mavlm_config& c = x->cfg;
   const size_t B = (size_t)nbatch(c);
+  const bool single = B == 1 && !rb_one;
   const size_t Rf = (size_t)c.mem_tokens * c.patches;          // memory rows of ONE video (row buffers: sized for all of them)
   const size_t R1 = (size_t)q_tokens(c) * c.patches;           // query rows of one video this context computes (row shard)
   const size_t R = Rf * B;                                     // rows of every row-wise operator (all videos stacked)
@@ -160,7 +178,7 @@ void carve(mavlm_ctx* x) {
   x->o_kv2 = 0;
   x->o_kvsplit = x->kvsplit_floats = 0;
   x->gsplit_floats = gemm_split_floats(c);
-  if (B == 1) {
+  if (single) {
     x->o_kv2 = o; o += al(S * 2 * L * Dp * 2);      // landing zone of mavlm_project_chunk_ahead
     // A projection made ahead runs on another stream than the step it overlaps, so it cannot borrow the step's split-K scratch
     // (o_gsplit: the planes of the step's own small-grid GEMMs).  It gets one of its own, sized for the plan the inline projection
@@ -198,7 +216,7 @@ void carve(mavlm_ctx* x) {
   {
     const size_t items = ((R1 + 127) / 128) * H;
     size_t fl = 0;
-    if (B == 1) {
+    if (single) {
       size_t cap;
       if (!wide_heads(c)) cap = items < 320 ? (512 / items > 8 ? 8 : 512 / items) : 0;      // mavlm_attention_splits
       else cap = (size_t)mavlm_attention_hd_splits((int)R1, 1 << 20, (int)H, nullptr);       // (its maximum over the key count)
@@ -221,6 +239,7 @@ void carve(mavlm_ctx* x) {
   // scratch of the frame-score variant of the last formation layer's forward (attention3.hip): (a, m) per (head, memory
   // row, frame) and the partial frame sums per (unit, 32-query group)
   x->o_fscr = x->o_fout = 0;
+  x->fscr_floats = x->fout_floats = 0;
   x->ftiles_ok = false;
   {
     const int fc = c.max_chunk_frames < 64 ? c.max_chunk_frames : 64;      // chunks of more frames take the column-sum pass
@@ -238,13 +257,16 @@ void carve(mavlm_ctx* x) {
         out = o2 > out ? o2 : out;
       }
       x->ftiles_ok = sup2;
+      x->fscr_floats = scr; x->fout_floats = out;
       x->o_fscr = o; o += al(scr * 4);
       x->o_fout = o; o += al(out * 4);
     } else if (wide_heads(c) && mavlm_attention_hd_frames_supported((int)R1, fc * c.patches, (int)(H * B), c.hidden / c.heads, c.patches) &&
                mavlm_attention_hd_frames_scr_floats((int)R1, fc * c.patches, (int)(H * B)) * 4 <= ((size_t)1 << 30)) {
       // head_dim 448 (attention_hd.hip): one 8-byte entry per (head, memory row, 32-key tile) - up to 1 GiB, else the column-sum pass
-      x->o_fscr = o; o += al(mavlm_attention_hd_frames_scr_floats((int)R1, fc * c.patches, (int)(H * B)) * 4);
-      x->o_fout = o; o += al(mavlm_attention_hd_frames_out_floats((int)R1, c.patches, (int)(H * B), c.patches) * 64 * 4);
+      x->fscr_floats = mavlm_attention_hd_frames_scr_floats((int)R1, fc * c.patches, (int)(H * B));
+      x->fout_floats = mavlm_attention_hd_frames_out_floats((int)R1, c.patches, (int)(H * B), c.patches) * 64;
+      x->o_fscr = o; o += al(x->fscr_floats * 4);
+      x->o_fout = o; o += al(x->fout_floats * 4);
     }
   }
   // scratch of the fused dense + residual + LayerNorm epilogue (gemm256.hip EPI_LN): {epoch, value} granules of the row
@@ -266,11 +288,57 @@ void carve(mavlm_ctx* x) {
   x->o_stage = 0;
   x->stage_bytes = fuse_stage_bytes(c, x->fuse_mems, x->gsplit_floats);
   if (x->stage_bytes) { x->o_stage = o; o += al(x->stage_bytes); }
-  x->o_q0 = o; o += al(R * Dp * 2);       // (LAST: no other offset moves)
+  x->o_q0 = o; o += al(R * Dp * 2);       // (behind every region above: none of their offsets moves)
+  x->total = o;
+}
+
+inline mavlm_ctx::nb_view view_of(const mavlm_ctx& t) {
+  mavlm_ctx::nb_view v;
+  v.gsplit_floats = t.gsplit_floats; v.split_floats = t.split_floats; v.lnx_bytes = t.lnx_bytes;
+  v.fscr_floats = t.fscr_floats; v.fout_floats = t.fout_floats; v.fscr = t.o_fscr != 0; v.ftiles_ok = t.ftiles_ok;
+  return v;
+}
+
+// The context's own carve, then - row batches - the views of the smaller video counts and the scratch they need beyond it.
+// The need is NOT monotone in the video count (the attention partials follow the plan): every count is carved and the
+// largest taken.  The additional regions sit behind o_q0, so a context only ever stepped with all B videos finds every
+// region where it was.
+void carve(mavlm_ctx* x) {
+  carve_core(x);
+  const int B = nbatch(x->cfg);
+  x->nb = B;
+  x->view[B] = view_of(*x);
+  x->o_xsplit = x->o_xgsplit = x->o_xfscr = x->o_xfout = 0;
+  if (B < 2) return;
+  mavlm_ctx::nb_view mx;
+  for (int v = 1; v < B; ++v) {
+    mavlm_ctx t;
+    t.cfg = x->cfg;
+    t.cfg.batch = v;
+    carve_core(&t, v == 1);
+    const mavlm_ctx::nb_view w = x->view[v] = view_of(t);
+    mx.gsplit_floats = w.gsplit_floats > mx.gsplit_floats ? w.gsplit_floats : mx.gsplit_floats;
+    mx.split_floats = w.split_floats > mx.split_floats ? w.split_floats : mx.split_floats;
+    mx.fscr_floats = w.fscr_floats > mx.fscr_floats ? w.fscr_floats : mx.fscr_floats;
+    mx.fout_floats = w.fout_floats > mx.fout_floats ? w.fout_floats : mx.fout_floats;
+  }
+  size_t o = x->total;
+  if (mx.split_floats > x->split_floats) { x->o_xsplit = o; o += al(mx.split_floats * 4); }
+  if (mx.gsplit_floats > x->gsplit_floats) { x->o_xgsplit = o; o += al(mx.gsplit_floats * 4); }
+  if (mx.fscr_floats > x->fscr_floats) { x->o_xfscr = o; o += al(mx.fscr_floats * 4); }
+  if (mx.fout_floats > x->fout_floats) { x->o_xfout = o; o += al(mx.fout_floats * 4); }
+  // (the exchange scratch of the fused Residual kernel grows with the rows: the own region covers every smaller count)
   x->total = o;
 }
 
 inline char* ws(mavlm_ctx* x, size_t off) { return (char*)x->b.workspace + off; }
+// what the step in flight decides by and where its count-dependent scratch lies (mavlm_ctx::view; the own carve for all B videos)
+inline const mavlm_ctx::nb_view& vw(const mavlm_ctx* x) { return x->view[x->nb]; }
+inline bool prefix_step(const mavlm_ctx* x) { return x->nb < nbatch(x->cfg); }
+inline float* p_gsplit(mavlm_ctx* x) { return (float*)ws(x, prefix_step(x) && x->o_xgsplit ? x->o_xgsplit : x->o_gsplit); }
+inline float* p_split(mavlm_ctx* x) { return (float*)ws(x, prefix_step(x) && x->o_xsplit ? x->o_xsplit : x->o_split); }
+inline float* p_fscr(mavlm_ctx* x) { return (float*)ws(x, prefix_step(x) && x->o_xfscr ? x->o_xfscr : x->o_fscr); }
+inline float* p_fout(mavlm_ctx* x) { return (float*)ws(x, prefix_step(x) && x->o_xfout ? x->o_xfout : x->o_fout); }
 
 #define MAVLM_TRY(expr)                       \
   do {                                        \
@@ -294,7 +362,7 @@ hipError_t gemm(int dtype, hipStream_t s, const void* A, int lda, const void* W,
 inline hipError_t gemm_x(mavlm_ctx* x, hipStream_t s, const void* A, int lda, const void* W, int ldw, const float* bias, void* C,
                          int ldc, int M, int N, int K, int epi) {
   return gemm(x->cfg.dtype, s, A, lda, W, ldw, bias, C, ldc, M, N, K, epi, nullptr, 0,
-              x->gsplit_floats ? (float*)ws(x, x->o_gsplit) : nullptr, x->gsplit_floats);
+              vw(x).gsplit_floats ? p_gsplit(x) : nullptr, vw(x).gsplit_floats);
 }
 
 // Residual block (MemoryController.py:26-29): out = LayerNorm(A . W^T + bias + res) * gamma + beta.  One kernel where the
@@ -304,7 +372,8 @@ inline hipError_t gemm_x(mavlm_ctx* x, hipStream_t s, const void* A, int lda, co
 int dense_ln(mavlm_ctx* x, hipStream_t s, const void* A, int lda, const void* W, int ldw, const float* bias, const void* res,
              const float* gamma, const float* beta, void* out, int rows, int N, int K) {
   const mavlm_config& c = x->cfg;
-  if (x->fused_ln && x->lnx_bytes && mavlm_gemm_ln_supported(rows, N, K, x->ln_wide) && mavlm_gemm_ln_ws_bytes(rows, N) <= x->lnx_bytes) {
+  if (x->fused_ln && vw(x).lnx_bytes && mavlm_gemm_ln_supported(rows, N, K, x->ln_wide) && mavlm_gemm_ln_ws_bytes(rows, N) <= vw(x).lnx_bytes &&
+      mavlm_gemm_ln_ws_bytes(rows, N) <= x->lnx_bytes) {
     if (!x->lnx_clean) {
       // the library owns the "zero before the first launch" invariant of the exchange scratch: one asynchronous memset on
       // the stream of the first step after mavlm_bind_buffers.  Not inside a capture: a replayed memset would reset the
@@ -326,17 +395,17 @@ int dense_ln(mavlm_ctx* x, hipStream_t s, const void* A, int lda, const void* W,
   }
   // small grids whose contraction is split (the 4D -> D projection at few memory tokens): the fp32 planes go straight into a
   // reduce + bias + residual + LayerNorm kernel - no reduction pass, no fp32 round trip of the dense output (same bits)
-  if (g_mavlm_splitk_ln && x->gsplit_floats && (N & 7) == 0 && N <= 4096 &&
+  if (g_mavlm_splitk_ln && vw(x).gsplit_floats && (N & 7) == 0 && N <= 4096 &&
       mavlm_gemm_split_ws_floats(rows, N, K, MAVLM_EPI_F32, N) != 0 &&
-      mavlm_gemm_split_ws_floats(rows, N, K, MAVLM_EPI_F32, N) <= x->gsplit_floats) {
+      mavlm_gemm_split_ws_floats(rows, N, K, MAVLM_EPI_F32, N) <= vw(x).gsplit_floats) {
     mavlm_gemm_args g;
     int planes = 0;
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.res = nullptr; g.ldr = 0; g.C = ws(x, x->o_pre); g.ldc = N;
     g.M = rows; g.N = N; g.K = K; g.epilogue = MAVLM_EPI_F32;
-    g.splitk_ws = (float*)ws(x, x->o_gsplit); g.planes_only = 1; g.planes_out = &planes;
+    g.splitk_ws = p_gsplit(x); g.planes_only = 1; g.planes_out = &planes;
     MAVLM_TRY(mavlm_launch_gemm(g, c.dtype, s));
     if (planes > 0) {
-      MAVLM_TRY(mavlm_launch_layernorm_planes((const float*)ws(x, x->o_gsplit), planes, bias, res, N, gamma, beta, out, rows, N,
+      MAVLM_TRY(mavlm_launch_layernorm_planes(p_gsplit(x), planes, bias, res, N, gamma, beta, out, rows, N,
                                               c.eps, c.dtype, s));
       return 0;
     }
@@ -356,7 +425,8 @@ int attn_block(mavlm_ctx* x, hipStream_t s, const mavlm_attn_weights& aw, const 
                const void* V, int ldv, long long kv_bs, int S, void* out, float* lse2, int frames = 0,
                int* frame_rows = nullptr, const void* q_pre = nullptr) {
   const mavlm_config& c = x->cfg;
-  const int B = nbatch(c), R1 = q_tokens(c) * c.patches, R = R1 * B, D = c.hidden, H = c.heads, dt = c.dtype,
+  // (B: the videos of this step - all of the context's, or the active prefix; Bc > 1: the row-batch rules)
+  const int B = x->nb, Bc = nbatch(c), R1 = q_tokens(c) * c.patches, R = R1 * B, D = c.hidden, H = c.heads, dt = c.dtype,
             Dp = padded_width(c);
   // q_pre: the projection of xq made earlier (the initial memory of a first step): no GEMM
   if (!q_pre) MAVLM_TRY(gemm_x(x, s, xq, D, aw.wq, D, aw.bq, ws(x, x->o_q), Dp, R, Dp, D, MAVLM_EPI_BIAS));
@@ -371,11 +441,11 @@ int attn_block(mavlm_ctx* x, hipStream_t s, const mavlm_attn_weights& aw, const 
     // it under the CURRENT tuning hooks.
     const int hd = c.hidden / c.heads;
     const bool sk = mavlm_attention_hd_streamk(R1, S, H * B, hd, nullptr) > 0;
-    if (sk) a.split_ws = mavlm_attention_hd_split_ws_floats(R1, S, H * B, hd) <= x->split_floats ? (float*)ws(x, x->o_split) : nullptr;
-    else a.split_ws = (B == 1 && x->split_floats) ? (float*)ws(x, x->o_split) : nullptr;
+    if (sk) a.split_ws = mavlm_attention_hd_split_ws_floats(R1, S, H * B, hd) <= vw(x).split_floats ? p_split(x) : nullptr;
+    else a.split_ws = (Bc == 1 && vw(x).split_floats) ? p_split(x) : nullptr;
     if (frames) {                             // forward + per-(row, tile) probability masses in one pass (no column-sum pass)
-      a.frame_scr = (float*)ws(x, x->o_fscr);
-      a.frame_out = (float*)ws(x, x->o_fout);
+      a.frame_scr = p_fscr(x);
+      a.frame_out = p_fout(x);
       a.frame_keys = c.patches;
       if (frame_rows) *frame_rows = mavlm_attention_hd_frames_rows_per_video(R1, H);
       MAVLM_TRY(mavlm_launch_attention_hd_frames(a, hd, dt, s));
@@ -386,18 +456,18 @@ int attn_block(mavlm_ctx* x, hipStream_t s, const mavlm_attn_weights& aw, const 
     // the schedule is part of the result: take it only when the carved workspace covers this shape's plan under the
     // CURRENT tuning hooks (they may have changed since mavlm_create) - never write past the carve
     // (a row batch never takes the split-KV form of the small grids: attention3.hip)
-    const size_t need = (B == 1 || mavlm_attention_streamk_wgs(R1, S, H * B) > 0) ? mavlm_attention_split_ws_floats(R1, S, H * B) : 0;
-    if (need > x->split_floats) return MAVLM_E_STATE;
-    a.split_ws = x->split_floats ? (float*)ws(x, x->o_split) : nullptr;
+    const size_t need = (Bc == 1 || mavlm_attention_streamk_wgs(R1, S, H * B) > 0) ? mavlm_attention_split_ws_floats(R1, S, H * B) : 0;
+    if (need > vw(x).split_floats) return MAVLM_E_STATE;
+    a.split_ws = vw(x).split_floats ? p_split(x) : nullptr;
     if (frames == 2) {                      // forward + per-(row, tile) masses: any schedule, incl. the split-KV small grids
-      a.frame_scr = (float*)ws(x, x->o_fscr);
-      a.frame_out = (float*)ws(x, x->o_fout);
+      a.frame_scr = p_fscr(x);
+      a.frame_out = p_fout(x);
       a.frame_keys = c.patches;
       if (frame_rows) *frame_rows = H * ((R1 + 63) / 64);
       MAVLM_TRY(mavlm_launch_attention3_frame_tiles(a, dt, s));
     } else if (frames) {                    // forward + per-frame probability mass in one pass (no column-sum pass)
-      a.frame_scr = (float*)ws(x, x->o_fscr);
-      a.frame_out = (float*)ws(x, x->o_fout);
+      a.frame_scr = p_fscr(x);
+      a.frame_out = p_fout(x);
       a.frame_keys = c.patches;
       if (frame_rows) *frame_rows = mavlm_attention_frames_rows_per_video(a);
       MAVLM_TRY(mavlm_launch_attention3_frames(a, dt, s));
@@ -415,15 +485,15 @@ int attn_block(mavlm_ctx* x, hipStream_t s, const mavlm_attn_weights& aw, const 
 // form of the 128-wide kernel (FR = 2: the small grids that split their keys; everywhere under mavlm_set_frame_score_mode(2))
 int step_frames_fused(const mavlm_ctx* x, int S) {
   const mavlm_config& c = x->cfg;
-  const int B = nbatch(c), R1 = q_tokens(c) * c.patches;
-  if (x->o_fscr == 0 || g_mavlm_frame_score_mode == 0) return 0;
+  const int B = x->nb, Bc = nbatch(c), R1 = q_tokens(c) * c.patches;
+  if (!vw(x).fscr || g_mavlm_frame_score_mode == 0) return 0;
   const bool fits = S <= (c.max_chunk_frames < 64 ? c.max_chunk_frames : 64) * c.patches;
   if (wide_heads(c))       // (any schedule: a (row, tile) entry has one writer under all of them)
     return fits && mavlm_attention_hd_frames_supported(R1, S, c.heads * B, c.hidden / c.heads, c.patches) ? 1 : 0;
   if (g_mavlm_attn_impl == 2) return 0;
-  const bool tiles = x->ftiles_ok && fits && mavlm_attention_frame_tiles_supported(R1, S, c.heads * B, c.patches);
+  const bool tiles = vw(x).ftiles_ok && fits && mavlm_attention_frame_tiles_supported(R1, S, c.heads * B, c.patches);
   if (g_mavlm_frame_score_mode == 2) return tiles ? 2 : 0;
-  if (B == 1) return mavlm_frame_scores_fused(R1, S, c.heads, c.patches) != 0 ? 1 : (tiles ? 2 : 0);
+  if (Bc == 1) return mavlm_frame_scores_fused(R1, S, c.heads, c.patches) != 0 ? 1 : (tiles ? 2 : 0);
   return mavlm_attention_frames_supported(R1, S, c.heads * B, c.patches) ? 1 : 0;
 }
 
@@ -442,13 +512,13 @@ size_t maps_floats(const mavlm_config& c) {
 // the pass behind one attention of the step: Q of the block sits in the workspace (q_used), lse2 in o_lse; one launch pair per video
 int step_maps(mavlm_ctx* x, hipStream_t s, const char* K, int ldk, long long kv_bs, int S, int k_group, int k_rot, size_t out_off) {
   const mavlm_config& c = x->cfg;
-  const int B = nbatch(c), Rq1 = q_tokens(c) * c.patches, H = c.heads, Dp = padded_width(c);
-  for (int b = 0; b < B; ++b) {
+  const int B = x->nb, Bc = nbatch(c), Rq1 = q_tokens(c) * c.patches, H = c.heads, Dp = padded_width(c);
+  for (int b = 0; b < B; ++b) {          // (the active videos; the scratch sits behind the maps of ALL the context's videos)
     mavlm_group_mass_args g;
     g.Q = (const char*)x->q_used + (size_t)b * Rq1 * Dp * 2; g.ldq = Dp; g.K = K + (size_t)b * kv_bs * 2; g.ldk = ldk;
     g.lse2 = (const float*)ws(x, x->o_lse) + (size_t)b * H * Rq1;
     g.out = x->maps + (size_t)b * maps_video_floats(c) + out_off;
-    g.scratch = x->maps + (size_t)B * maps_video_floats(c);
+    g.scratch = x->maps + (size_t)Bc * maps_video_floats(c);
     g.R = Rq1; g.S = S; g.H = H; g.scale = attn_scale(c); g.q_group = c.patches; g.k_group = k_group; g.k_rot = k_rot;
     MAVLM_TRY(mavlm_launch_group_mass(g, wide_heads(c) ? c.hidden / c.heads : 128, c.dtype, s));
   }
@@ -459,11 +529,13 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
   const mavlm_config& c = x->cfg;
   // R1: memory rows of one video (keys of the evolution, ring strides); Rq1: the rows of them this context computes (row
   // shard: q_tokens memory tokens from row r0 on; else all); R: rows of the row-wise operators
-  const int B = nbatch(c), R1 = c.mem_tokens * c.patches, Rq1 = q_tokens(c) * c.patches, r0 = q_row0(c), R = Rq1 * B,
+  // B: the videos this step serves (x->nb: all Bc videos of the context, or the active prefix of a ragged row batch - their
+  // rows come first in every stacked operand and in a ring slot); Bc: the videos of the context (ring strides, row-batch rules)
+  const int B = x->nb, Bc = nbatch(c), R1 = c.mem_tokens * c.patches, Rq1 = q_tokens(c) * c.patches, r0 = q_row0(c), R = Rq1 * B,
             D = c.hidden, I = c.inter, L = c.depth, H = c.heads, dt = c.dtype;
   const int Dp = padded_width(c);
   const int S = F * c.patches;
-  const size_t slot_bytes = (size_t)R1 * B * D * 2;           // one FIFO slot: the newest memory of every video, [B, R1, D]
+  const size_t slot_bytes = (size_t)R1 * Bc * D * 2;          // one FIFO slot: the newest memory of every video, [Bc, R1, D]
   const int cap = c.cache_cap;
   const int n = x->steps < cap ? x->steps : cap;
   // evolution K/V ring: [B][cap][R1][2 Dp] - the keys of ONE video are contiguous over its slots
@@ -487,7 +559,7 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
       mavlm_gemm_args g;
       g.A = mem_new; g.lda = D; g.W = x->w.w_kv_evo; g.ldw = D; g.bias = x->w.b_kv_evo; g.res = nullptr; g.ldr = 0;
       g.C = kv_new; g.ldc = 2 * Dp; g.M = R1 * B; g.N = 2 * Dp; g.K = D; g.epilogue = MAVLM_EPI_BIAS;
-      if (B > 1) { g.c_rpb = R1; g.c_nb = B; g.c_bstride = evo_bs; }
+      if (Bc > 1) { g.c_rpb = R1; g.c_nb = B; g.c_bstride = evo_bs; }
       else if (x->gsplit_floats && mavlm_gemm_split_ws_floats(R1, 2 * Dp, D, MAVLM_EPI_BIAS, 2 * Dp) <= x->gsplit_floats)
         g.splitk_ws = (float*)ws(x, x->o_gsplit);
       MAVLM_TRY(mavlm_launch_gemm(g, dt, s));
@@ -511,7 +583,7 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
   // projection made for this step but another chunk is discarded (its buffer is waited for before anything overwrites it).
   int rb = 0;
   bool pre = false;
-  if (B == 1) {
+  if (Bc == 1) {
     hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s, &cst);
     const bool capturing = cst != hipStreamCaptureStatusNone;
@@ -549,14 +621,21 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
     // goes stale exactly when the packed mem0 it also reads does.
     const void* q_pre = nullptr;
     if (l == 0 && x->steps == 0 && g_mavlm_cache_q0) {
-      if (!x->q0_valid) {
+      // (a prefix step reads the rows of a projection made for more videos where neither splits its contraction: the GEMM is
+      //  row-independent then; otherwise it projects its own rows again, as a context of that many videos would)
+      const size_t qneed = mavlm_gemm_split_ws_floats(R, Dp, D, MAVLM_EPI_BIAS, Dp);
+      const bool qsplit = qneed != 0 && qneed <= vw(x).gsplit_floats;
+      bool hit = x->q0_valid && (B == x->q0_nb || (B < x->q0_nb && !x->q0_split && !qsplit));
+      if (!hit) {
         hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(s, &cst) == hipSuccess && cst == hipStreamCaptureStatusNone) {
           MAVLM_TRY(gemm_x(x, s, cur, D, x->w.layer_attn[0].wq, D, x->w.layer_attn[0].bq, ws(x, x->o_q0), Dp, R, Dp, D, MAVLM_EPI_BIAS));
-          x->q0_valid = true;
+          x->q0_valid = hit = true;
+          x->q0_nb = B;
+          x->q0_split = qsplit;
         }
       }
-      if (x->q0_valid) q_pre = ws(x, x->o_q0);
+      if (hit) q_pre = ws(x, x->o_q0);
     }
     int rc = attn_block(x, s, x->w.layer_attn[l], cur, Kl, ldkv, Vl, ldkv, (long long)S * ldkv, S, ws(x, x->o_a), lse,
                         fused_scores, &frows, q_pre);
@@ -566,7 +645,7 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
       if (rc) return rc;
     }
     if (fused_scores) {
-      MAVLM_TRY(mavlm_launch_frame_finish((const float*)ws(x, x->o_fout), frows, B, F, c.patches, frame_scores, scores_f32, dt, s));
+      MAVLM_TRY(mavlm_launch_frame_finish(p_fout(x), frows, B, F, c.patches, frame_scores, scores_f32, dt, s));
     } else if (want_scores) {
       for (int b = 0; b < B; ++b) {          // (one pass per video: the column-sum kernels know nothing of the row batch)
         mavlm_colsum_args ca;
@@ -597,7 +676,7 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
     }
     cur = dst;
   }
-  if (B == 1 && x->o_kv2) {          // the chunk K/V buffer this step read is free once the stream gets here
+  if (Bc == 1 && x->o_kv2) {         // the chunk K/V buffer this step read is free once the stream gets here
     hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s, &cst);
     if (cst == hipStreamCaptureStatusNone && x->ev_done[rb]) {
@@ -606,6 +685,8 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
     }
   }
   x->steps += 1;   // append; the slot written above evicts the oldest entry once the ring is full (:152-154)
+  for (int b = 0; b < B; ++b) x->vsteps[b] += 1;
+  x->n_active = B;
   return 0;
 }
 
@@ -799,6 +880,7 @@ int mavlm_bind_weights(mavlm_ctx* x, const mavlm_weights* w) {
   }
   x->w = *w;
   x->q0_valid = false;                          // (so is the projection of the previous initial memory)
+  x->q0_nb = 0;
   x->pre[0].seg = x->pre[1].seg = nullptr;      // K/V projected with the previous weights are not this context's any more
   x->has_w = true;
   return 0;
@@ -829,6 +911,9 @@ int mavlm_ln_status_async(mavlm_ctx* x, void* host16, int32_t clear, void* strea
 int mavlm_reset(mavlm_ctx* x) {
   if (!x) return MAVLM_E_ARG;
   x->steps = 0;
+  x->n_active = 0;
+  for (int b = 0; b < MAVLM_MAX_BATCH; ++b) x->vsteps[b] = 0;
+  x->nb = nbatch(x->cfg);
   x->pre[0].seg = x->pre[1].seg = nullptr;      // (a projection still in flight keeps its `pending` mark: the next writer waits)
   return 0;
 }
@@ -858,7 +943,30 @@ int mavlm_step_batch(mavlm_ctx* x, const void* const* segs, int32_t F, void* fra
   if (F <= 0 || F > x->cfg.max_chunk_frames) return MAVLM_E_SHAPE;
   for (int b = 0; b < nbatch(x->cfg); ++b)
     if (!segs[b]) return MAVLM_E_ARG;
+  if (x->n_active != 0 && x->n_active < nbatch(x->cfg)) return MAVLM_E_STATE;      // (the prefix of a ragged batch never grows)
+  x->nb = nbatch(x->cfg);
   return step_impl(x, segs, F, frame_scores, scores_f32, (hipStream_t)stream);
+}
+
+int mavlm_step_batch_active(mavlm_ctx* x, const void* const* segs, int32_t n_active, int32_t F, void* frame_scores,
+                            int32_t scores_f32, void* stream) {
+  if (!x || !segs) return MAVLM_E_ARG;
+  if (n_active < 1 || n_active > nbatch(x->cfg)) return MAVLM_E_ARG;
+  if (nbatch(x->cfg) < 2) return MAVLM_E_STATE;            // (a single video steps through mavlm_step)
+  if (!x->has_w || !x->has_b) return MAVLM_E_STATE;
+  if (F <= 0 || F > x->cfg.max_chunk_frames) return MAVLM_E_SHAPE;
+  for (int b = 0; b < n_active; ++b)
+    if (!segs[b]) return MAVLM_E_ARG;
+  if (x->n_active != 0 && n_active > x->n_active) return MAVLM_E_STATE;            // all videos start together; the prefix only shrinks
+  x->nb = n_active;
+  const int rc = step_impl(x, segs, F, frame_scores, scores_f32, (hipStream_t)stream);
+  x->nb = nbatch(x->cfg);
+  return rc;
+}
+
+int mavlm_video_steps(const mavlm_ctx* x, int32_t b) {
+  if (!x || b < 0 || b >= nbatch(x->cfg)) return MAVLM_E_ARG;
+  return x->vsteps[b];
 }
 
 int mavlm_batch(const mavlm_ctx* x) { return x ? nbatch(x->cfg) : MAVLM_E_ARG; }
@@ -950,6 +1058,8 @@ int fuse_emit_impl(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_id
   const int B = nbatch(c), R1 = c.mem_tokens * c.patches, R = R1 * B, D = c.hidden, I = c.inter, dt = c.dtype, cap = c.cache_cap;
   const int n = x->steps < cap ? x->steps : cap;
   if (n == 0) return MAVLM_E_STATE;
+  for (int b = 0; b < B; ++b)       // (a ragged row batch - videos with fewer steps - emits through mavlm_fuse_emit_layout_ragged_to)
+    if (x->vsteps[b] != x->steps) return MAVLM_E_STATE;
   // block rows: the memory block and the fine-frame block are laid out SEPARATELY (llava_arch.py:585-634 runs per feature)
   const int64_t r_mem = n_mem_prompt, mem_rows = block_rows((int64_t)n * R1, layout, gap);
   const int64_t r_fp = r_mem + mem_rows, r_fine = r_fp + n_frame_prompt, fine_rows = block_rows((int64_t)n_fine * c.patches, layout, gap);
@@ -1058,6 +1168,115 @@ int mavlm_fuse_emit_layout_batch_to(mavlm_ctx* x, const void* const* x_pe, const
   if (nbatch(x->cfg) < 2) return MAVLM_E_STATE;             // (a single video: mavlm_fuse_emit_layout writes where `out` points)
   return fuse_emit_impl(x, x_pe, fine_idx, n_fine, mem_prompt, n_mem_prompt, frame_prompt, n_frame_prompt, newline, with_frames,
                         layout, out, out_rows, rows, (hipStream_t)stream, dst_row);
+}
+
+namespace {
+// mavlm_fuse_emit_layout_ragged_to.  Videos 0 .. nv-1 in the context's longest-first order: vsteps is non-increasing, so the
+// videos that hold a ring slot, and the videos with one block length, are ranges that start at video 0 / are contiguous.
+int ragged_emit_impl(mavlm_ctx* x, int nv, const void* const* x_pe, const int64_t* fine_idx, int32_t n_fine, const void* mem_prompt,
+                     int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt, const void* newline,
+                     int32_t with_frames, int32_t layout, void* out, int64_t out_rows, const int64_t* dst_row, int64_t* rows,
+                     hipStream_t s) {
+  const mavlm_config& c = x->cfg;
+  const int Bc = nbatch(c), R1 = c.mem_tokens * c.patches, D = c.hidden, I = c.inter, dt = c.dtype, cap = c.cache_cap;
+  if (nv < 1 || nv > Bc || nv > MAVLM_VBASE_MAX) return MAVLM_E_ARG;
+  if (n_mem_prompt < 0 || n_frame_prompt < 0 || n_fine < 0 || (n_mem_prompt && !mem_prompt) ||
+      (with_frames && ((n_frame_prompt && !frame_prompt) || (n_fine && (!x_pe || !fine_idx)))))
+    return MAVLM_E_ARG;
+  const int gap = layout_gap(c, layout);
+  if (gap < 0) return gap;
+  if (layout != MAVLM_LAYOUT_NONE && !newline) return MAVLM_E_ARG;
+  if ((((uintptr_t)mem_prompt | (uintptr_t)newline | (uintptr_t)frame_prompt | (uintptr_t)out | (uintptr_t)fine_idx) & 15) || (D & 7))
+    return MAVLM_E_ARG;
+  // per video: memories, place of the first fine-frame row, block length; then the destinations - on the host, before the first launch
+  int nm[MAVLM_VBASE_MAX];
+  int64_t need[MAVLM_VBASE_MAX], r_fine[MAVLM_VBASE_MAX];
+  const int64_t fine_rows = block_rows((int64_t)n_fine * c.patches, layout, gap);
+  for (int b = 0; b < nv; ++b) {
+    nm[b] = x->vsteps[b] < cap ? x->vsteps[b] : cap;
+    const int64_t r_fp = n_mem_prompt + block_rows((int64_t)nm[b] * R1, layout, gap);
+    r_fine[b] = r_fp + n_frame_prompt;
+    need[b] = with_frames ? r_fine[b] + fine_rows : r_fp;
+  }
+  for (int b = 0; b < nv; ++b) {
+    if (dst_row[b] < 0 || dst_row[b] > out_rows - need[b]) return MAVLM_E_ARG;
+    for (int a = 0; a < b; ++a)
+      if (dst_row[a] < dst_row[b] + need[b] && dst_row[b] < dst_row[a] + need[a]) return MAVLM_E_ARG;
+  }
+  if (!x->has_w || !x->has_b) return MAVLM_E_STATE;
+  if (!x->w.w_f1 || !x->w.b_f1 || !x->w.w_f2 || !x->w.b_f2_type0 || (with_frames && !x->w.type1)) return MAVLM_E_STATE;
+  for (int b = 0; b < nv; ++b) {
+    if (nm[b] == 0 || (b > 0 && x->vsteps[b] > x->vsteps[b - 1])) return MAVLM_E_STATE;
+    if (with_frames && n_fine && !x_pe[b]) return MAVLM_E_ARG;
+  }
+  const size_t rowb = (size_t)D * 2;
+  // ---- the literal rows: one launch per range of videos with the same number of memories (the rows of copy_rows_kernel's runs
+  // are the same for all of them); the blocks' first rows travel as per-video bases
+  long long base[MAVLM_VBASE_MAX];
+  for (int b = 0; b < nv; ++b) base[b] = (long long)dst_row[b] * D;
+  for (int b0 = 0; b0 < nv;) {
+    int b1 = b0 + 1;
+    while (b1 < nv && nm[b1] == nm[b0]) ++b1;
+    const int64_t feat = (int64_t)nm[b0] * R1, mem_rows = block_rows(feat, layout, gap), r_fp = n_mem_prompt + mem_rows;
+    const int nl_mem = (int)(mem_rows - feat), nl_fine = (int)(fine_rows - (int64_t)n_fine * c.patches);
+    const void* src[4] = {mem_prompt, newline, frame_prompt, newline};
+    const int cnt[4] = {n_mem_prompt, nl_mem, with_frames ? n_frame_prompt : 0, with_frames ? nl_fine : 0};
+    const long long dst[4] = {0, n_mem_prompt + (gap > 0 ? gap : feat), r_fp, r_fine[b0] + (gap > 0 ? gap : (int64_t)n_fine * c.patches)};
+    const int rep[4] = {0, gap > 0 ? gap + 1 : 0, 0, gap > 0 ? gap + 1 : 0};
+    MAVLM_TRY(mavlm_launch_copy_rows(src, cnt, dst, 4, out, 0, b1 - b0, D, s, rep, base + b0));
+    b0 = b1;
+  }
+  // ---- the fused memories, per ring slot: the videos that hold slot `sl` are 0 .. h-1; video b has it as the p-th memory of its
+  // block.  Consecutive slots that all Bc videos hold at consecutive places share a GEMM pair, as in fuse_emit_impl (their
+  // rows are contiguous in the ring then); a slot of fewer videos runs alone over its first h * R1 rows.
+  auto holders = [&](int sl) { int h = 0; while (h < nv && sl < nm[h]) ++h; return h; };
+  auto place = [&](int b, int sl) { return x->vsteps[b] <= cap ? sl : (sl - x->vsteps[b] % cap + cap) % cap; };
+  const int nb_keep = x->nb;
+  for (int sl = 0; sl < cap;) {
+    const int h = holders(sl);
+    if (h == 0) break;
+    int run = 1;
+    while (h == Bc && run < x->fuse_mems && sl + run < cap && holders(sl + run) == Bc) {
+      bool next = true;
+      for (int b = 0; b < h && next; ++b) next = place(b, sl + run) == place(b, sl) + run;
+      if (!next) break;
+      ++run;
+    }
+    const int rows_ = run * h * R1;
+    long long vb[MAVLM_VBASE_MAX];
+    for (int b = 0; b < h; ++b) {
+      const int64_t v0 = (int64_t)place(b, sl) * R1;                 // (a multiple of the gap: whole frames)
+      vb[b] = base[b] + (long long)(n_mem_prompt + v0 + (gap > 0 ? v0 / gap : 0)) * D;
+    }
+    const char* mem = (const char*)x->b.mem_ring + (size_t)sl * Bc * R1 * rowb;
+    x->nb = h;                  // (the plan of a context of h videos: gemm_x, as mavlm_fuse_emit_layout_batch_to there)
+    const hipError_t e1 = gemm_x(x, s, mem, D, x->w.w_f1, D, x->w.b_f1, ws(x, x->o_h), I, rows_, I, D, MAVLM_EPI_GELU);
+    x->nb = nb_keep;
+    MAVLM_TRY(e1);
+    mavlm_gemm_args g = fuser_out_gemm(c, rows_, out, nullptr, 0);
+    g.A = ws(x, x->o_h); g.W = x->w.w_f2; g.bias = x->w.b_f2_type0;
+    g.c_rpb = R1; g.c_nb = h; g.c_bstride = 0; g.c_vbase = vb; g.c_gap = gap;
+    MAVLM_TRY(mavlm_launch_gemm(g, dt, s));
+    sl += run;
+  }
+  if (with_frames && n_fine) {
+    long long fb[MAVLM_VBASE_MAX];
+    for (int b = 0; b < nv; ++b) fb[b] = base[b] + (long long)r_fine[b] * D;
+    MAVLM_TRY(mavlm_launch_row_add_batch(x_pe, fine_idx, x->w.type1, out, 0, nv, n_fine, c.patches, D, dt, s, gap, fb, n_fine));
+  }
+  for (int b = 0; b < nv; ++b) rows[b] = need[b];
+  return 0;
+}
+}  // namespace
+
+int mavlm_fuse_emit_layout_ragged_to(mavlm_ctx* x, int32_t n_videos, const void* const* x_pe, const int64_t* fine_idx,
+                                     int32_t n_fine, const void* mem_prompt, int32_t n_mem_prompt, const void* frame_prompt,
+                                     int32_t n_frame_prompt, const void* newline, int32_t with_frames, int32_t layout, void* out,
+                                     int64_t out_rows, const int64_t* dst_row, int64_t* rows, void* stream) {
+  if (!x || !out || !rows || !dst_row || out_rows < 0) return MAVLM_E_ARG;
+  if (nbatch(x->cfg) < 2) return MAVLM_E_STATE;
+  return ragged_emit_impl(x, n_videos, x_pe, fine_idx, n_fine, mem_prompt, n_mem_prompt, frame_prompt, n_frame_prompt, newline,
+                          with_frames, layout, out, out_rows, dst_row, rows, (hipStream_t)stream);
 }
 
 int mavlm_fuse_emit(mavlm_ctx* x, const void* x_pe, const int64_t* fine_idx, int32_t n_fine, const void* mem_prompt,

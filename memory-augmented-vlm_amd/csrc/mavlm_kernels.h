@@ -269,9 +269,10 @@ hipError_t mavlm_launch_row_add(const void* x, const int64_t* src, const void* t
 // row_add for B videos in one launch: out[b*vstride + (t*P + p)*D ..] = x[b][src[t], p, :] + table_row[:]  (x = HOST array of B
 // device pointers; vstride in elements)
 // gap > 0: output row r of a video lands r / gap rows further down (the newline rows of a token layout, see c_gap)
+// src_vstride (with vbase; 0 = the videos share `src`): video b gathers through src + b * src_vstride - one index row per video
 hipError_t mavlm_launch_row_add_batch(const void* const* x, const int64_t* src, const void* table_row, void* out,
                                       long long vstride, int B, int T, int P, int D, int dtype, hipStream_t s, int gap = 0,
-                                      const long long* vbase = nullptr);
+                                      const long long* vbase = nullptr, long long src_vstride = 0);
 
 // `runs` (<= 4) literal row runs: out[b*vstride + (dst[i]+r)*D ..] = src[i][r*D ..] for r < n[i], every video b < B
 // (vstride in elements); one launch for the prompt / newline rows of mavlm_fuse_emit

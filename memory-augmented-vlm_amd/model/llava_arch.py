@@ -305,7 +305,7 @@ def video_memory_tokens_batched(model, bp: BatchedProjector, images, frame_idx_c
                                 memory_prompt_embeds: torch.Tensor, frame_prompt_embeds: torch.Tensor,
                                 image_newline: Optional[torch.Tensor], with_frames: bool = True, chunk: int = 32,
                                 fine_frames: int = 32, out: Optional[torch.Tensor] = None, layout: str = "one_token",
-                                dst_rows: Optional[List[int]] = None):
+                                dst_rows: Optional[List[int]] = None, ragged: bool = False):
     """`video_memory_tokens` for B videos of the SAME length stepped together (row batch, `BatchedProjector`): every
     weight-shared GEMM / LayerNorm of the path runs once over the stacked memory rows of all videos.  `images`: B tensors
     [T,196,D]; `frame_idx_cpu`: the original frame indices (shared: same length, same sampling).  Returns
@@ -313,8 +313,14 @@ def video_memory_tokens_batched(model, bp: BatchedProjector, images, frame_idx_c
     `frame_idx_cpu` may be a list of B index tensors of one length (_batch_pe_frames).
     `dst_rows` (with `out` = a contiguous [out_rows, D] buffer, e.g. the padded inputs_embeds of a batch of samples seen as
     rows): video b's block is written at row dst_rows[b] of `out` (mavlm_fuse_emit_layout_batch_to: the same launches, one
-    destination per video; rows outside the blocks are not touched); returns (out, info) with info["block_rows"]."""
+    destination per video; rows outside the blocks are not touched); returns (out, info) with info["block_rows"].
+    `ragged=True`: 2 .. B videos whose lengths are multiples of `chunk` and may differ (`_video_memory_tokens_ragged`); returns
+    (list of [rows_b, D] blocks in the caller's order - or `out` with `dst_rows` -, info).  Without it unequal shapes are
+    refused."""
     layout_period(layout, images[0].shape[1])
+    if ragged:
+        return _video_memory_tokens_ragged(model, bp, images, frame_idx_cpu, memory_prompt_embeds, frame_prompt_embeds,
+                                           image_newline, with_frames, chunk, fine_frames, out, layout, dst_rows)
     B = bp.batch
     if len(images) != B:
         raise capi.MavlmError(f"video_memory_tokens_batched: {B} videos expected")
@@ -372,6 +378,81 @@ def video_memory_tokens_batched(model, bp: BatchedProjector, images, frame_idx_c
                                                        ctypes.byref(written), ops.stream_ptr()), "mavlm_fuse_emit_layout_batch")
     assert written.value == rows
     return out, info
+
+
+def _video_memory_tokens_ragged(model, bp, images, frame_idx_cpu, memory_prompt_embeds, frame_prompt_embeds, image_newline,
+                                with_frames, chunk, fine_frames, out, layout, dst_rows):
+    """`video_memory_tokens_batched(ragged=True)`: k videos (2 <= k <= bp.batch) of T_b = c_b * `chunk` frames on one row-batched
+    engine.  Internally the videos are ordered by chunk count, longest first (stable); step i takes chunk i of the videos that
+    still have one - a prefix that only shrinks (`BatchedProjector.step`) -; ONE emit at the end writes every video's block
+    (`mavlm_fuse_emit_layout_ragged_to`: per ring slot the fuser runs over the videos that hold it; a fine-frame index row per
+    video).  The blocks come back in the caller's order."""
+    k = len(images)
+    if not 2 <= k <= bp.batch:
+        raise capi.MavlmError(f"video_memory_tokens_batched(ragged=True): 2..{bp.batch} videos expected")
+    P, D = images[0].shape[1:]
+    dev, dt = images[0].device, images[0].dtype
+    for im in images:
+        if not im.is_cuda or im.dim() != 3 or tuple(im.shape[1:]) != (P, D) or im.dtype != dt or im.device != dev:
+            raise capi.MavlmError("video_memory_tokens_batched: GPU frame tokens [T_b, P, D] of one dtype / device expected")
+        if im.shape[0] < chunk or im.shape[0] % chunk:
+            raise capi.MavlmError(f"video_memory_tokens_batched(ragged=True): every video length must be a positive multiple of "
+                                  f"the chunk ({chunk} frames); got {im.shape[0]}")
+    if not isinstance(frame_idx_cpu, (list, tuple)) or len(frame_idx_cpu) != k or \
+            any(i.numel() != im.shape[0] for i, im in zip(frame_idx_cpu, images)):
+        raise capi.MavlmError("video_memory_tokens_batched(ragged=True): one frame index tensor per video, of its length")
+    pe: TemporalPositionalEncoding = model.positional_encoding
+    rm: TransformerProjector = model.recurrent_memory_transformer
+    order = sorted(range(k), key=lambda i: -images[i].shape[0])            # longest first; stable in the caller's order
+    xs, fines = [], []
+    for i in order:
+        pe.check_indices(frame_idx_cpu[i])
+        xs.append(pe(images[i], _device_indices(frame_idx_cpu[i], dev), indices_checked=True))      # :510-511
+        fines.append(fine_frame_indices(images[i].shape[0], fine_frames))                           # :513-522
+    n_fine = fines[0].numel()
+    if any(f.numel() != n_fine for f in fines):
+        raise capi.MavlmError("video_memory_tokens_batched(ragged=True): the videos must have the same number of fine frames")
+    chunks = [x.shape[0] // chunk for x in xs]
+    bp.reset()                                                                                      # :532
+    for i in range(chunks[0]):                                                                      # :534-537, per video
+        bp.step([x[i * chunk:(i + 1) * chunk] for x, c in zip(xs, chunks) if c > i])
+    eng = bp.engine(dev, dt)
+    mp = memory_prompt_embeds.to(dt).contiguous()
+    fp = frame_prompt_embeds.to(dt).contiguous()
+    nl, nl_ptr = _newline_ptr(image_newline, layout, dev, dt)
+    R = rm.num_memory_tokens * P
+    rows = [video_token_rows(x.shape[0], rm.num_memory_tokens, P, with_frames, chunk, fine_frames, eng.c.cache_cap, mp.shape[0],
+                             fp.shape[0], layout) for x in xs]
+    if dst_rows is not None:
+        if out is None or out.dim() != 2 or out.shape[1] != D or out.dtype != dt or not out.is_contiguous() or not out.is_cuda \
+                or len(dst_rows) != k:
+            raise capi.MavlmError(f"video_memory_tokens_batched: `dst_rows` needs {k} rows of a contiguous [out_rows,{D}] {dt} "
+                                  "GPU tensor `out`")
+        buf, dst = out, [int(dst_rows[i]) for i in order]
+    else:
+        if out is not None:
+            raise capi.MavlmError("video_memory_tokens_batched(ragged=True): `out` goes with `dst_rows` (the blocks differ in length)")
+        buf = torch.empty((sum(rows), D), device=dev, dtype=dt)
+        dst = [sum(rows[:j]) for j in range(k)]
+    import ctypes
+    written = (ctypes.c_int64 * k)()
+    xptrs = (capi.vp * k)(*[x.data_ptr() for x in xs])
+    fine_dev = _device_indices(torch.cat(fines), dev)                        # [k, n_fine], one row per video
+    capi.check(capi.lib().mavlm_fuse_emit_layout_ragged_to(eng.ctx, k, xptrs, fine_dev.data_ptr(), n_fine, mp.data_ptr(), mp.shape[0],
+                                                           fp.data_ptr(), fp.shape[0], nl_ptr, 1 if with_frames else 0,
+                                                           capi.LAYOUTS[layout], buf.data_ptr(), buf.shape[0],
+                                                           (ctypes.c_int64 * k)(*dst), written, ops.stream_ptr()),
+               "mavlm_fuse_emit_layout_ragged_to")
+    assert list(written) == rows
+    back = [0] * k                               # caller's position -> position in the engine's order
+    for j, i in enumerate(order):
+        back[i] = j
+    info = {"order": order, "num_memories": [min(chunks[back[i]], eng.c.cache_cap) for i in range(k)],
+            "pe_frames": [xs[back[i]] for i in range(k)], "fine_idx": [fines[back[i]] for i in range(k)],
+            "block_rows": [rows[back[i]] for i in range(k)], "frame_scores": bp.frame_scores}
+    if dst_rows is not None:
+        return out, info
+    return [buf[dst[back[i]]:dst[back[i]] + rows[back[i]]] for i in range(k)], info
 
 
 def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame_idx_cpu,
@@ -453,6 +534,62 @@ def plan_row_batches(keys, sizes=ROW_BATCH_SIZES):
         singles += members[at:]
     batches.sort(key=lambda b: b[0])
     return batches, sorted(singles)
+
+
+RAGGED_MAX_GROUP = 8
+
+
+def plan_ragged_batches(lengths, chunk=32, keys=None, sizes=ROW_BATCH_SIZES):
+    """Which videos of a forward step together when a row batch may hold videos of different lengths (ragged row batches).
+    `lengths`: the sampled frame count of each video, in input order; a video is eligible when its length is a positive multiple
+    of `chunk` - its chunk count is length / chunk.  `keys`: one hashable per video with what else has to agree inside a batch
+    (dtype, device) - default: nothing.
+    Eligible videos with one key are sorted by chunk count, longest first, stable in input order.  A video joins the current
+    group while the group has fewer than 8 videos and its chunk count is at least HALF that of the group's longest video;
+    otherwise it opens a new group.  A group of k >= 2 videos runs on ONE row-batched engine: the smallest size in `sizes`
+    that is >= k (3 -> 4, 5 / 6 / 7 -> 8), stepped as a shrinking prefix.  Groups of one and the videos that are not eligible
+    go where they go today: through `plan_row_batches` over (length, key).
+    The "half" bound limits the stretch a lone survivor runs on the row-batch schedule at one video; it is a policy picked
+    WITHOUT a measurement (tools/diag_ragged_batch.py reports what a lopsided pair costs).
+    Returns (ragged, batches, singles): `ragged` = [(engine size, positions longest first)], the groups in the order of their
+    first (longest) video; `batches`, `singles` = as `plan_row_batches` returns them, for the rest."""
+    sizes_up = sorted({int(s) for s in sizes})
+    if any(s < 2 or s > 16 for s in sizes_up):
+        raise ValueError("row batch sizes: 2 .. 16 videos")
+    n = len(lengths)
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("plan_ragged_batches: chunk >= 1")
+    chunk_counts = [int(t) // chunk if int(t) > 0 and int(t) % chunk == 0 else 0 for t in lengths]
+    keys = [None] * n if keys is None else list(keys)
+    if len(keys) != n:
+        raise ValueError("plan_ragged_batches: one key per video")
+    cap = min(RAGGED_MAX_GROUP, sizes_up[-1]) if sizes_up else 0
+    by_key = {}
+    for i, c in enumerate(chunk_counts):
+        if c > 0:
+            by_key.setdefault(keys[i], []).append(i)
+    ragged, taken = [], set()
+    for members in by_key.values():
+        members = sorted(members, key=lambda i: -int(chunk_counts[i]))       # (stable: input order among equal counts)
+        groups, cur = [], []
+        for i in members:
+            if cur and len(cur) < cap and 2 * int(chunk_counts[i]) >= int(chunk_counts[cur[0]]):
+                cur.append(i)
+            else:
+                if cur:
+                    groups.append(cur)
+                cur = [i]
+        if cur:
+            groups.append(cur)
+        for g in groups:
+            if len(g) >= 2:
+                ragged.append((next(s for s in sizes_up if s >= len(g)), g))
+                taken.update(g)
+    ragged.sort(key=lambda sg: min(sg[1]))
+    rest = [i for i in range(n) if i not in taken]
+    batches, singles = plan_row_batches([(int(lengths[i]), keys[i]) for i in rest], sizes)
+    return ragged, [[rest[j] for j in b] for b in batches], [rest[j] for j in singles]
 
 
 class VideoPlacement:
@@ -542,7 +679,7 @@ def features_per_sample(video_of, tokens):
 
 
 def run_video_groups(model, videos, mem_prompt, frame_prompt, image_newline, with_frames=True, layout="one_token",
-                     sizes=ROW_BATCH_SIZES, train=False, out=None, dst_rows=None, single=None):
+                     sizes=ROW_BATCH_SIZES, train=False, out=None, dst_rows=None, single=None, ragged=False):
     """The memory path for several videos on the current stream - the ONE place that groups videos into row batches.
     `videos`: (pooled frame tokens [T, P, D], original frame indices [T] on the host) per video.  Videos with the same sampled
     frame count, dtype and device form a group (they share chunk bounds and fine-frame indices); `plan_row_batches` cuts it into
@@ -551,14 +688,30 @@ def run_video_groups(model, videos, mem_prompt, frame_prompt, image_newline, wit
       out is None   -> returns the token blocks [rows_v, D] in input order (`train`: under autograd, through
                        video_memory_tokens_batched_train / the autograd path of video_memory_tokens)
       out, dst_rows -> inference: video v's block is written at row dst_rows[v] of the contiguous [out_rows, D] buffer `out`:
-                       one emit per row batch (mavlm_fuse_emit_layout_batch_to), the `out=` slice for a single; returns None."""
+                       one emit per row batch (mavlm_fuse_emit_layout_batch_to), the `out=` slice for a single; returns None.
+    `ragged` (LlavaMetaForCausalLM.enable_ragged_row_batches; inference - under autograd the grouping above stays): videos whose
+    sampled length is a multiple of the 32-frame chunk are grouped by `plan_ragged_batches` instead - different chunk counts
+    in one row batch, one ragged emit per group (`video_memory_tokens_batched(ragged=True)`); the rest as above."""
     rm = model.recurrent_memory_transformer
-    batches, singles = plan_row_batches([(v[0].shape[0], v[0].dtype, str(v[0].device)) for v in videos], sizes)
+    groups = []
+    if ragged and not train:
+        groups, batches, singles = plan_ragged_batches([v[0].shape[0] for v in videos], 32,
+                                                       [(v[0].dtype, str(v[0].device)) for v in videos], sizes)
+    else:
+        batches, singles = plan_row_batches([(v[0].shape[0], v[0].dtype, str(v[0].device)) for v in videos], sizes)
     if single is None:
         def single(frames, idx, o):
             return video_memory_tokens(model, frames, idx, mem_prompt, frame_prompt, image_newline, with_frames, out=o,
                                        layout=layout)[0]
     tokens = [None] * len(videos)
+    for size, grp in groups:
+        bp = rm.row_batcher(size)
+        toks = video_memory_tokens_batched(model, bp, [videos[i][0] for i in grp], [videos[i][1] for i in grp], mem_prompt,
+                                           frame_prompt, image_newline, with_frames, out=out, layout=layout,
+                                           dst_rows=None if out is None else [dst_rows[i] for i in grp], ragged=True)[0]
+        if out is None:
+            for j, i in enumerate(grp):
+                tokens[i] = toks[j]
     for grp in batches:
         bp = rm.row_batcher(len(grp))
         frames, idxs = [videos[i][0] for i in grp], [videos[i][1] for i in grp]
@@ -987,7 +1140,7 @@ class LlavaMetaForCausalLM:
         train = path_wants_grad(model, mem_prompt, frame_prompt, newline)
         if train or plan.general or not vids[0][0].is_cuda or any(p.device != dev or p.dtype != dt for p, _ in vids):
             tokens = run_video_groups(model, vids, mem_prompt, frame_prompt, newline, not drop, layout, self.row_batch_sizes,
-                                      train=train)
+                                      train=train, ragged=self._ragged_row_batches and not train)
             return splice_into_text(self, model, features_per_sample(plan.video_of, tokens), input_ids, position_ids,
                                     attention_mask, past_key_values, labels)
         # in place: the padded buffer once, text rows from embed_tokens, padding zeroed, every block emitted where it belongs
@@ -1002,12 +1155,24 @@ class LlavaMetaForCausalLM:
             at += hi - lo
         with torch.no_grad():
             run_video_groups(model, vids, mem_prompt, frame_prompt, newline, not drop, layout, self.row_batch_sizes,
-                             out=emb.view(B * L, D), dst_rows=plan.dst_row)
+                             out=emb.view(B * L, D), dst_rows=plan.dst_row, ragged=self._ragged_row_batches)
         if text is not None and text.dtype != dt:
             emb = emb.to(text.dtype)
         lab_list = None if labels is None else [l[m] for l, m in zip(labels, mask)]
         out_labels, out_mask, out_pos = plan.labels_mask_positions(lab_list, attention_mask, position_ids)
         return None, _pos_skipping(self, out_pos, emb), out_mask, past_key_values, emb, out_labels
+
+    _ragged_row_batches = False
+
+    def enable_ragged_row_batches(self, on: bool = True):
+        """Several videos per forward: let a row batch hold videos of DIFFERENT lengths (off by default).  Off, videos step
+        together only when their sampled frame counts are equal (`plan_row_batches`); everything else runs as single videos.
+        On, every video whose sampled length is a multiple of the 32-frame chunk - the sampler turns every video of 32 or more
+        frames into one - is grouped by `plan_ragged_batches`: up to 8 videos whose chunk counts differ by at most a factor of
+        two share one row-batched engine, ordered longest first and stepped as a shrinking prefix, with one ragged emit per
+        group into the padded `inputs_embeds`.  Inference; a forward that records a graph keeps the grouping of the switch off.
+        The hipGraph cache and `MemoryPathPool` are not affected."""
+        self._ragged_row_batches = bool(on)
 
     # -- hipGraph replay for repeated video shapes (round 4) -------------------------------------------------------------
     def enable_memory_graphs(self, capacity: int = 4):

@@ -270,11 +270,12 @@ class _Engine:
         capi.check(lib.mavlm_bind_attention_maps(self.ctx, buf.data_ptr(), n), "mavlm_bind_attention_maps")
         self.maps = buf
 
-    def read_maps(self, F: int, n_past: int):
-        """copies of the maps the last step wrote: (formation [B, depth, H, M, F], evolution [B, H, M, n_past] | None)"""
+    def read_maps(self, F: int, n_past: int, n_active=None):
+        """copies of the maps the last step wrote: (formation [B, depth, H, M, F], evolution [B, H, M, n_past] | None); a step
+        over a prefix of the videos (`n_active`) wrote the maps of those videos only"""
         c = self.c
         M = c.q_tokens if c.q_tokens > 0 else c.mem_tokens
-        B = max(self.batch, 1)
+        B = max(self.batch, 1) if n_active is None else int(n_active)
         nf = c.depth * c.heads * M * c.max_chunk_frames
         per = nf + c.heads * M * c.cache_cap
         v = self.maps[:B * per].view(B, per)
@@ -711,7 +712,12 @@ class BatchedProjector:
     R = M*196 memory rows of that one video.  Those operators are row-independent and the weights are shared, so the rows
     of B videos stack into ONE [B*R, D] operand per launch (`mavlm_config.batch`): at the reference's M = 8 that turns
     1568-row GEMMs (7 of 256 CUs' worth of tiles) into chip-filling ones; the attention serves B*heads (video, head)
-    pairs, each video over its own keys.  Videos of a batch step with the same chunk sizes (same length).
+    pairs, each video over its own keys.  Videos of a batch step with the same chunk sizes; they may differ in their NUMBER of
+    chunks (a ragged row batch): all videos start together, ordered longest first, and `step` takes the chunks of a prefix of
+    them that only ever shrinks (`mavlm_step_batch_active`) - a step over k >= 2 videos is, launch for launch and bit for bit,
+    the step of a `BatchedProjector` of size k.  Video b then holds `video_steps(b)` steps: `memory_cache(b)` returns its own
+    FIFO, and the entries of `frame_scores` / `attention_maps` of a step have a leading axis of that step's video count (video
+    b is in the first `video_steps(b)` of them).
 
         bp = BatchedProjector(rm, 8)
         bp.reset()
@@ -740,6 +746,8 @@ class BatchedProjector:
         self.record_attention_maps = False    # True: every step appends an AttentionMaps with a leading video axis
         self.attention_maps: List[AttentionMaps] = []
         self._n = 0
+        self._active = 0                      # videos of the last `step` (0: none since `reset`)
+        self._vsteps = [0] * self.batch       # steps of each video since `reset`
         self._mode = None                     # "engine" (step) / "autograd" (step_train) once a video batch has started
         self._tcache = []                     # training path: the cached memories, stacked [B*R, D] graph tensors, oldest first
         self._tevo = []                       # ... and their evolution K/V projections ([B, R, Dp] views), one pair per entry
@@ -765,6 +773,8 @@ class BatchedProjector:
         self.frame_scores = []
         self.attention_maps = []
         self._n = 0
+        self._active = 0
+        self._vsteps = [0] * self.batch
         self._mode = None
         self._tcache, self._tevo = [], []
         if self._engine is not None:
@@ -775,9 +785,12 @@ class BatchedProjector:
 
     @torch.no_grad()
     def step(self, segs):
-        """one chunk of every video: segs = B tensors [F, P, D] (contiguous, same F)"""
-        if len(segs) != self.batch:
-            raise capi.MavlmError(f"BatchedProjector.step: {self.batch} chunks expected")
+        """one chunk of every video: segs = B tensors [F, P, D] (contiguous, same F) - or, in a ragged row batch, of the first
+        len(segs) videos: 2 .. B chunks at the first step of a batch, afterwards 1 .. the count of the step before"""
+        k = len(segs)
+        if (self._active == 0 and not 2 <= k <= self.batch) or (self._active and not 1 <= k <= self._active):
+            raise capi.MavlmError(f"BatchedProjector.step: {self.batch} chunks expected (a ragged batch: 2..{self.batch} at the "
+                                  f"first step, then no more than the step before - {self._active or self.batch}); got {k}")
         F, P, D = segs[0].shape
         for t in segs:
             if not t.is_cuda or tuple(t.shape) != (F, P, D) or not t.is_contiguous() or t.dtype != segs[0].dtype:
@@ -789,18 +802,25 @@ class BatchedProjector:
                                   "before running the inference step")
         self._mode = "engine"
         eng = self.engine(segs[0].device, segs[0].dtype, F)
-        ptrs = (capi.vp * self.batch)(*[t.data_ptr() for t in segs])
-        scores = torch.empty((self.batch, F), device=segs[0].device, dtype=segs[0].dtype) if self.compute_frame_scores else None
+        ptrs = (capi.vp * k)(*[t.data_ptr() for t in segs])
+        scores = torch.empty((k, F), device=segs[0].device, dtype=segs[0].dtype) if self.compute_frame_scores else None
         record = bool(self.record_attention_maps)
         if record and torch.cuda.is_current_stream_capturing():
             raise capi.MavlmError("record_attention_maps: the maps are written by eager steps, not inside a graph capture")
         eng.set_maps(record)
         n_past = capi.lib().mavlm_cache_len(eng.ctx)
-        capi.check(capi.lib().mavlm_step_batch(eng.ctx, ptrs, F, scores.data_ptr() if scores is not None else 0, 0,
-                                               ops.stream_ptr()), "mavlm_step_batch")
+        if k == self.batch:
+            capi.check(capi.lib().mavlm_step_batch(eng.ctx, ptrs, F, scores.data_ptr() if scores is not None else 0, 0,
+                                                   ops.stream_ptr()), "mavlm_step_batch")
+        else:
+            capi.check(capi.lib().mavlm_step_batch_active(eng.ctx, ptrs, k, F, scores.data_ptr() if scores is not None else 0, 0,
+                                                          ops.stream_ptr()), "mavlm_step_batch_active")
         if record:
-            self.attention_maps.append(AttentionMaps(*eng.read_maps(F, n_past)))
+            self.attention_maps.append(AttentionMaps(*eng.read_maps(F, n_past, k)))
         self._n += 1
+        self._active = k
+        for b in range(k):
+            self._vsteps[b] += 1
         if scores is not None:
             self.frame_scores.append(scores)
         return scores
@@ -859,6 +879,7 @@ class BatchedProjector:
             m = ag.mlp_block(layer, a)
         self._tcache.append(m)                                      # :152
         self._n += 1
+        self._vsteps = [v + 1 for v in self._vsteps]
         if len(self._tcache) > cap:
             drop = len(self._tcache) - cap
             self._tcache = self._tcache[drop:]
@@ -904,5 +925,10 @@ class BatchedProjector:
             return [m.view(self.batch, proj.num_memory_tokens, proj.patch_size, proj.hidden_size)[b] for m in self._tcache]
         eng = self._engine
         cap = eng.c.cache_cap
-        n = min(self._n, cap)
-        return [eng.mem_ring[(self._n - n + i) % cap, b] for i in range(n)]
+        steps = self._vsteps[b]              # (video b's own steps: a ragged row batch leaves its ring rows as its last step did)
+        n = min(steps, cap)
+        return [eng.mem_ring[(steps - n + i) % cap, b] for i in range(n)]
+
+    def video_steps(self, b: int) -> int:
+        """steps video b has taken since `reset` (`mavlm_video_steps` after `step`)"""
+        return self._vsteps[b]
