@@ -406,6 +406,20 @@ int64_t mavlm_attention_colsum_floats(int32_t R, int32_t S, int32_t H);
 int mavlm_attention_colsum_plan(int32_t R, int32_t S, int32_t H, int32_t info[2]);
 int mavlm_attention_colsum(const void* Q, int32_t ldq, const void* K, int32_t ldk, const float* lse2, float* part,
                            int64_t part_floats, int32_t R, int32_t S, int32_t H, float scale, int32_t dtype, void* stream);
+/* Row-batched column sums: ONE launch (plus one plane reduction) serves nb independent videos - the frame scores of a row
+ * batch's training step.  H counts the heads of ONE video (unlike mavlm_attention_batch).  Q holds the nb x R query rows video after
+ * video ([nb*R, >= H*w], w = 128 for head_dim <= 128 - narrower heads zero-padded - or 448); video b's S keys start
+ * b * kv_bstride elements into K (>= S * ldk: a video's keys end before the next one's start; ignored for nb = 1); lse2 is
+ * [nb*H, R], the layout mavlm_attention_batch writes.  Every video runs the schedule of mavlm_attention_colsum(_hd) on its own
+ * operands (a second grid dimension; the loads of a ragged last tile never reach the next video's rows), no atomics: the result
+ * equals nb single launches bit for bit.  `part` holds mavlm_attention_colsum_batch_floats(R,S,H,nb) = nb *
+ * mavlm_attention_colsum_floats(R,S,H) floats; video b's [H,S] result starts b * mavlm_attention_colsum_floats(R,S,H) floats into it.
+ * All arguments are checked before anything is enqueued: MAVLM_E_ARG for a null pointer, nb < 1, nb > MAVLM_MAX_BATCH, bad
+ * strides (kv_bstride < S * ldk included) or too small a `part`; MAVLM_E_SHAPE for a head_dim other than <= 128 or 448. */
+int64_t mavlm_attention_colsum_batch_floats(int32_t R, int32_t S, int32_t H, int32_t nb);
+int mavlm_attention_colsum_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk, int64_t kv_bstride, const float* lse2,
+                                 float* part, int64_t part_floats, int32_t R, int32_t S, int32_t H, int32_t nb, int32_t head_dim,
+                                 float scale, int32_t dtype, void* stream);
 /* Attention maps: the mass of the normalised probabilities per (head, query group, key group),
  *   out[h][i][j] = sum over q in query group i, k in key group j of softmax(scale * Q_h K_h^T)[q][k]     fp32,
  * [H, ceil(R/q_group), ceil(S/k_group)] for groups of q_group consecutive rows and k_group consecutive keys (the last group

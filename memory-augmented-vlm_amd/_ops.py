@@ -338,6 +338,31 @@ def attention_batch(q, k, v, heads, nb, want_lse=False, head_dim=128, scale=None
     return out, lse
 
 
+def attention_colsum_batch(q, k, lse2, heads, nb, head_dim=128, scale=None):
+    """`attention_colsum` for nb videos in ONE launch (`mavlm_attention_colsum_batch`): q [nb*R, >=heads*w] holds the videos' query
+    rows one after the other, k is a [nb, S, >=heads*w] view (w = 128, or 448 for the wide heads), lse2 [nb*heads, R] as
+    `attention_batch` returns it; `heads` per video.  Every video runs the single-video schedule: bit-identical to nb
+    `attention_colsum` calls.  Returns [nb, heads, S] fp32 (a view of the pass's plane buffer)."""
+    _need_gpu(q, k, lse2)
+    RB, _, ldq = _rows(q)
+    S, ldk, kbs = _kv_batch(k, nb, "attention_colsum_batch")
+    hw = 448 if head_dim == 448 else 128
+    W = heads * hw
+    if RB % nb or q.shape[1] < W or k.shape[2] < W or k.dtype != q.dtype or lse2.dtype != torch.float32 \
+            or not lse2.is_contiguous() or lse2.numel() != nb * heads * (RB // nb):
+        raise capi.MavlmError("attention_colsum_batch: operand mismatch (stacked query rows, K with one video stride, lse2 "
+                              "[nb*heads, R] fp32)")
+    R = RB // nb
+    lib = capi.lib()
+    per = int(lib.mavlm_attention_colsum_floats(R, S, heads))
+    buf = torch.empty((nb, per), device=q.device, dtype=torch.float32)
+    capi.check(lib.mavlm_attention_colsum_batch(q.data_ptr(), ldq, k.data_ptr(), ldk, kbs, lse2.data_ptr(), buf.data_ptr(),
+                                                buf.numel(), R, S, heads, nb, head_dim,
+                                                1.0 / math.sqrt(float(head_dim)) if scale is None else float(scale),
+                                                dtype_code(q.dtype), stream_ptr()), "mavlm_attention_colsum_batch")
+    return buf[:, :heads * S].view(nb, heads, S)
+
+
 def attention_bwd_batch(q, k, v, o, do, lse2, heads, nb, need_dq=True, need_dk=True, need_dv=True, scale=None, head_dim=128,
                         dk_out=None, dv_out=None):
     """Gradients of `attention_batch` in one launch per output (`mavlm_attention_bwd_batch`; head_dim 448 is routed to

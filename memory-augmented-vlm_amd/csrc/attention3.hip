@@ -405,6 +405,13 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   qk_plain(IC<0>{}, 0);
+  // The first iteration issues the DMA of K(2) into K slot 0 - the slot qk_plain has just read.  Every wave must be done with
+  // those reads first: a wave that other work on its SIMD held back (a kernel of another stream) was still reading K(0) while
+  // a faster wave's pieces of K(2), or the zeros of a tile past the last one, landed in it (its 32 queries then came out with
+  // other bits, seen with two videos in flight on two streams).
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
   if (nt == 1 && (S & (KT3 - 1))) mask_tail(IC<0>{}, 0);
   max_and_rescale(IC<0>{});
 
@@ -1307,12 +1314,26 @@ constexpr int CS3_LDS = 2 * TILE3 + 512;
 constexpr int CS3_QPF = 2;                     // LDS read-ahead of the Q fragments, in MFMA steps (4 VGPRs each; the
                                                // kernel must stay within 128 VGPRs for four workgroups per CU)
 
-template <typename T>
+// Row batch (NB): blockIdx.y is the video.  Its workgroups run the per-video schedule unchanged on that video's operands: Q, K,
+// lse2 and part are rebased here, once, so the buffer descriptors below start at the video and end at its last row - a ragged
+// last Q tile reads zeros, never the next video's rows.  The single-video instantiation takes an empty argument.
+template <bool NB> struct cs3_batch_arg {};
+template <> struct cs3_batch_arg<true> { long long kv_bstride, part_bstride; };
+
+template <typename T, bool NB = false>
 __global__ __launch_bounds__(256, 4) void attn_colsum3_kernel(const uint16_t* __restrict__ Q, int ldq,
                                                               const uint16_t* __restrict__ K, int ldk,
                                                               const float* __restrict__ lse2, float* __restrict__ part,
-                                                              int R, int S, int H, float c, int nkb, int nplanes) {
+                                                              int R, int S, int H, float c, int nkb, int nplanes,
+                                                              cs3_batch_arg<NB> vb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  if constexpr (NB) {
+    const size_t b = blockIdx.y;
+    Q += b * (size_t)R * ldq;
+    K += b * (size_t)vb.kv_bstride;
+    lse2 += b * (size_t)H * R;
+    part += b * (size_t)vb.part_bstride;
+  }
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1520,9 +1541,11 @@ __global__ __launch_bounds__(256, 4) void attn_colsum3_kernel(const uint16_t* __
 }
 
 // part[0] += part[1] + ... in plane order (stand-alone operator: the result is the first H*S floats)
-__global__ void colsum_planes_reduce_kernel(float* __restrict__ part, size_t n, int nplanes) {
+// (row batch: blockIdx.y is the video, its planes start vstride floats after the previous video's)
+__global__ void colsum_planes_reduce_kernel(float* __restrict__ part, size_t n, int nplanes, size_t vstride) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  part += blockIdx.y * vstride;
   float v = part[i];
   for (int p = 1; p < nplanes; ++p) v += part[(size_t)p * n + i];
   part[i] = v;
@@ -1573,21 +1596,33 @@ hipError_t mavlm_launch_colsum3(const mavlm_colsum_args& a, int dtype, hipStream
   const float c = a.scale * 1.44269504088896340736f;
   const int nkb = (a.S + 127) / 128;
   if ((double)nkb * a.H * ((a.R + KT3 - 1) / KT3) >= 2.0e9) return hipErrorInvalidValue;   // 32-bit schedule arithmetic
+  const int nb = a.nb > 0 ? a.nb : 1;
+  if (nb > 65535) return hipErrorInvalidValue;
   int planes = 1;
-  const int G = mavlm_colsum_plan(a.R, a.S, a.H, &planes);
+  const int G = mavlm_colsum_plan(a.R, a.S, a.H, &planes);       // the per-video schedule, for every video
   {
-    mavlm_prof_scope prof(MAVLM_K_COLSUM, 2.0 * a.R * (double)a.S * a.H * HD3, 2.0 * HD3 * a.H * ((double)a.R + a.S), s);
-    if (dtype == MAVLM_F16)
-      hipLaunchKernelGGL(attn_colsum3_kernel<F16>, dim3(G), dim3(256), CS3_LDS, s, (const uint16_t*)a.Q, a.ldq,
-                         (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, nkb, planes);
-    else
-      hipLaunchKernelGGL(attn_colsum3_kernel<BF16>, dim3(G), dim3(256), CS3_LDS, s, (const uint16_t*)a.Q, a.ldq,
-                         (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, nkb, planes);
+    mavlm_prof_scope prof(MAVLM_K_COLSUM, 2.0 * nb * a.R * (double)a.S * a.H * HD3, 2.0 * nb * HD3 * a.H * ((double)a.R + a.S), s);
+    if (nb > 1) {
+      const cs3_batch_arg<true> vb = {a.kv_bstride, a.part_bstride};
+      if (dtype == MAVLM_F16)
+        hipLaunchKernelGGL((attn_colsum3_kernel<F16, true>), dim3(G, nb), dim3(256), CS3_LDS, s, (const uint16_t*)a.Q, a.ldq,
+                           (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, nkb, planes, vb);
+      else
+        hipLaunchKernelGGL((attn_colsum3_kernel<BF16, true>), dim3(G, nb), dim3(256), CS3_LDS, s, (const uint16_t*)a.Q, a.ldq,
+                           (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, nkb, planes, vb);
+    } else if (dtype == MAVLM_F16) {
+      hipLaunchKernelGGL((attn_colsum3_kernel<F16, false>), dim3(G), dim3(256), CS3_LDS, s, (const uint16_t*)a.Q, a.ldq,
+                         (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, nkb, planes, cs3_batch_arg<false>{});
+    } else {
+      hipLaunchKernelGGL((attn_colsum3_kernel<BF16, false>), dim3(G), dim3(256), CS3_LDS, s, (const uint16_t*)a.Q, a.ldq,
+                         (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, nkb, planes, cs3_batch_arg<false>{});
+    }
   }
   if (!a.keep_planes && planes > 1) {
     const size_t n = (size_t)a.H * a.S;
-    mavlm_prof_scope prof(MAVLM_K_MISC, 0.0, 4.0 * (planes + 1) * (double)n, s);
-    hipLaunchKernelGGL(colsum_planes_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, n, planes);
+    mavlm_prof_scope prof(MAVLM_K_MISC, 0.0, 4.0 * nb * (planes + 1) * (double)n, s);
+    hipLaunchKernelGGL(colsum_planes_reduce_kernel, dim3((unsigned)((n + 255) / 256), nb), dim3(256), 0, s, a.part, n, planes,
+                       (size_t)(nb > 1 ? a.part_bstride : 0));
   }
   return hipGetLastError();
 }

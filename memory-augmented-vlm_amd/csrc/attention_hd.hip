@@ -889,13 +889,21 @@ template <typename T, int HD>
 __global__ __launch_bounds__(256, 1) void attn_colsum_hd_kernel(const uint16_t* __restrict__ Q, int ldq,
                                                                 const uint16_t* __restrict__ K, int ldk,
                                                                 const float* __restrict__ lse2, float* __restrict__ part,
-                                                                int R, int S, int H, float c) {
+                                                                int R, int S, int H, float c,
+                                                                long long kv_bstride, long long part_bstride) {
   constexpr int NSUB = (HD + 127) / 128;
   constexpr int SUB = KTH * 256;
   constexpr int TILE = NSUB * SUB;
   constexpr int KS = HD / 16;                             // k-steps of the 32x32x16 MFMA
   constexpr int NCH = HD / 8;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 Q slots
+  {   // row batch: blockIdx.y is the video; everything below runs on its operands alone (rows are clamped to ITS last row)
+    const size_t b = blockIdx.y;
+    Q += b * (size_t)R * ldq;
+    K += b * (size_t)kv_bstride;
+    lse2 += b * (size_t)H * R;
+    part += b * (size_t)part_bstride;
+  }
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1075,8 +1083,11 @@ hipError_t launch_colsum_hd(const mavlm_colsum_args& a, hipStream_t s) {
     if (e != hipSuccess) return e;
   }
   const float c = a.scale * 1.44269504088896340736f;
-  hipLaunchKernelGGL(kern, dim3(((a.S + 127) / 128) * a.H), dim3(256), LDS, s, (const uint16_t*)a.Q, a.ldq, (const uint16_t*)a.K,
-                     a.ldk, a.lse2, a.part, a.R, a.S, a.H, c);
+  const int nb = a.nb > 0 ? a.nb : 1;
+  if (nb > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kern, dim3(((a.S + 127) / 128) * a.H, nb), dim3(256), LDS, s, (const uint16_t*)a.Q, a.ldq, (const uint16_t*)a.K,
+                     a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, (long long)(nb > 1 ? a.kv_bstride : 0),
+                     (long long)(nb > 1 ? a.part_bstride : 0));
   return hipGetLastError();
 }
 

@@ -1503,6 +1503,44 @@ int mavlm_attention_colsum(const void* Q, int32_t ldq, const void* K, int32_t ld
   return e == hipErrorInvalidValue ? MAVLM_E_ARG : (int)e;
 }
 
+// ---- row-batched column sums: nb videos per launch, every video on the single-video schedule (the bits of nb launches)
+int64_t mavlm_attention_colsum_batch_floats(int32_t R, int32_t S, int32_t H, int32_t nb) {
+  return (R > 0 && S > 0 && H > 0 && nb >= 1 && nb <= MAVLM_MAX_BATCH) ? (int64_t)nb * (int64_t)mavlm_colsum_part_floats(R, S, H) : 0;
+}
+
+int mavlm_attention_colsum_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk, int64_t kv_bstride, const float* lse2,
+                                 float* part, int64_t part_floats, int32_t R, int32_t S, int32_t H, int32_t nb, int32_t head_dim,
+                                 float scale, int32_t dtype, void* stream) {
+  // every check comes before any launch
+  if (!Q || !K || !lse2 || !part || R <= 0 || S <= 0 || H <= 0 || nb < 1 || nb > MAVLM_MAX_BATCH || (dtype != 0 && dtype != 1))
+    return MAVLM_E_ARG;
+  if (head_dim != 448 && (head_dim <= 0 || head_dim > 128)) return MAVLM_E_SHAPE;
+  const int hw = head_dim == 448 ? 448 : 128;                  // columns a head occupies (narrow heads: zero-padded to 128)
+  if ((ldq & 7) || (ldk & 7) || (kv_bstride & 7) || ldq < H * hw || ldk < H * hw) return MAVLM_E_ARG;
+  if (nb > 1 && kv_bstride < (int64_t)S * ldk) return MAVLM_E_ARG;           // a video's keys end before the next video's start
+  const int64_t per = (int64_t)mavlm_colsum_part_floats(R, S, H);
+  if (part_floats < (int64_t)nb * per) return MAVLM_E_ARG;
+  if (hw == 128 && ((double)R * ldq * 2.0 >= 2147483648.0 || (double)((S + 127) / 128) * H * ((R + 63) / 64) >= 2.0e9))
+    return MAVLM_E_ARG;                                         // the 32-bit offsets / schedule arithmetic of the pipelined kernel
+  mavlm_colsum_args a;
+  a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.lse2 = lse2; a.part = part; a.R = R; a.S = S; a.H = H; a.scale = scale;
+  a.nb = nb; a.kv_bstride = kv_bstride; a.part_bstride = per;
+  hipError_t e = hipSuccess;
+  if (hw == 448) {
+    e = mavlm_launch_colsum_hd(a, 448, dtype, (hipStream_t)stream);
+  } else if (g_mavlm_attn_impl != 2) {
+    e = mavlm_launch_colsum3(a, dtype, (hipStream_t)stream);
+  } else {                                                     // the register-staged diagnostic kernel knows one video
+    a.nb = 1;
+    for (int b = 0; b < nb && e == hipSuccess; ++b) {
+      a.Q = (const uint16_t*)Q + (size_t)b * R * ldq; a.K = (const uint16_t*)K + (size_t)b * kv_bstride;
+      a.lse2 = lse2 + (size_t)b * H * R; a.part = part + (size_t)b * per;
+      e = mavlm_launch_colsum(a, dtype, (hipStream_t)stream);
+    }
+  }
+  return e == hipErrorInvalidValue ? MAVLM_E_ARG : (int)e;
+}
+
 int64_t mavlm_attention_group_mass_floats(int32_t R, int32_t S, int32_t H, int32_t q_group, int32_t k_group) {
   return (R > 0 && S > 0 && H > 0 && q_group > 0 && k_group > 0) ? (int64_t)mavlm_group_mass_floats(R, S, H, q_group, k_group) : 0;
 }

@@ -217,6 +217,12 @@ struct mavlm_colsum_args {
   int R, S, H;
   float scale;
   int keep_planes = 0;
+  // row batch (attn_colsum3_kernel, attn_colsum_hd_kernel): the launch serves nb independent videos.  H stays the heads of ONE
+  // video; Q holds the nb x R query rows of the videos one after the other, lse2 is [nb*H, R] (the layout the batched forward
+  // writes), video b's keys start b * kv_bstride elements into K and its planes b * part_bstride floats into part
+  // ([nb][planes][H][S]).  Every video runs the single-video schedule on its own operands: the bits of nb single launches.
+  int nb = 1;
+  long long kv_bstride = 0, part_bstride = 0;
 };
 // column-sum pass of the head_dim-128 kernels: workgroups of the balanced schedule / planes of `part` (attention3.hip)
 int mavlm_colsum_plan(int R, int S, int H, int* planes);

@@ -464,7 +464,8 @@ def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame
     over the B * n * M * 196 stacked memory rows (HIP autograd Functions); the token-type adds, the layout and the concatenation
     are torch ops, so autograd routes the gradients of token_type_embedding, the prompt embeddings and image_newline as in the
     reference.  Returns (tokens [B, rows, D] with grad - the bits of `video_memory_tokens_batched` -, info).
-    `frame_idx_cpu`: shared, or a list of one index tensor per video (_batch_pe_frames)."""
+    `frame_idx_cpu`: shared, or a list of one index tensor per video (_batch_pe_frames).  Videos of different lengths:
+    `video_memory_tokens_ragged_train`."""
     from .. import _autograd as ag
     layout_period(layout, images[0].shape[1])
     B = bp.batch
@@ -506,6 +507,97 @@ def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame
             "memory_rows": (mp.shape[0], mp.shape[0] + (mem_rows if layout_period(layout, P) else n * R)),
             "frame_scores": bp.frame_scores}
     return torch.stack(toks), info
+
+
+def _ragged_fuser_rows(lib, counts, R, D, inter):
+    """Does the fuser's GEMM pair give the same bits over ALL stacked FIFO rows as over the rows of the videos that hold one
+    ring slot (the grouping of `mavlm_fuse_emit_layout_ragged_to`)?  The kernels are row-independent; only a split contraction -
+    `mavlm_linear_ws_floats`, a function of the row count - sums in another order.  `counts`: memories per video, longest first."""
+    rows = {sum(counts) * R} | {sum(1 for c in counts if c > sl) * R for sl in range(max(counts))}
+    return all(lib.mavlm_linear_ws_floats(m, inter, D, capi.EPI_GELU, inter) == 0 and
+               lib.mavlm_linear_ws_floats(m, D, inter, capi.EPI_BIAS, D) == 0 for m in rows)
+
+
+def video_memory_tokens_ragged_train(model, bp: BatchedProjector, images, frame_idx_cpu, memory_prompt_embeds: torch.Tensor,
+                                     frame_prompt_embeds: torch.Tensor, image_newline: Optional[torch.Tensor],
+                                     with_frames: bool = True, chunk: int = 32, fine_frames: int = 32, layout: str = "one_token"):
+    """`video_memory_tokens_batched(ragged=True)` under autograd - the ragged form of `video_memory_tokens_batched_train`: 2 .. B
+    videos whose lengths are positive multiples of `chunk` and may differ, one frame index tensor each, the same number of fine
+    frames.  The videos are ordered longest first (stable) and stepped by `BatchedProjector.step_train(ragged=True)`; the fuser
+    runs over all videos' FIFO rows in one stacked GEMM pair where no row count involved splits its contraction, else in one
+    pair per ring slot over the videos that hold it - either way the feature rows are the ragged inference block's bits.  Type
+    rows, layout and concatenation are torch ops, as on the equal-length path.  Returns (list of [rows_b, D] blocks with grad
+    in the caller's order, the info of the ragged inference call: `order`, per-video `num_memories`, `block_rows`, ...)."""
+    from .. import _autograd as ag
+    layout_period(layout, images[0].shape[1])
+    k = len(images)
+    if not 2 <= k <= bp.batch:
+        raise capi.MavlmError(f"video_memory_tokens_ragged_train: 2..{bp.batch} videos expected")
+    P, D = images[0].shape[1:]
+    dev, dt = images[0].device, images[0].dtype
+    for im in images:
+        if not im.is_cuda or im.dim() != 3 or tuple(im.shape[1:]) != (P, D) or im.dtype != dt or im.device != dev:
+            raise capi.MavlmError("video_memory_tokens_batched_train: GPU frame tokens [T_b, P, D] of one dtype / device expected")
+        if im.shape[0] < chunk or im.shape[0] % chunk:
+            raise capi.MavlmError(f"video_memory_tokens_ragged_train: every video length must be a positive "
+                                  f"multiple of the chunk ({chunk} frames); got {im.shape[0]}")
+    if not isinstance(frame_idx_cpu, (list, tuple)) or len(frame_idx_cpu) != k or \
+            any(i.numel() != im.shape[0] for i, im in zip(frame_idx_cpu, images)):
+        raise capi.MavlmError("video_memory_tokens_ragged_train: one frame index tensor per video, of its length")
+    pe: TemporalPositionalEncoding = model.positional_encoding
+    rm: TransformerProjector = model.recurrent_memory_transformer
+    order = sorted(range(k), key=lambda i: -images[i].shape[0])            # longest first; stable in the caller's order
+    xs, fines = [], []
+    for i in order:
+        pe.check_indices(frame_idx_cpu[i])
+        xs.append(pe(images[i], _device_indices(frame_idx_cpu[i], dev), indices_checked=True))      # :510-511
+        fines.append(fine_frame_indices(images[i].shape[0], fine_frames))                           # :513-522
+    n_fine = fines[0].numel()
+    if any(f.numel() != n_fine for f in fines):
+        raise capi.MavlmError("video_memory_tokens_ragged_train: the videos must have the same number of fine frames")
+    chunks = [x.shape[0] // chunk for x in xs]
+    bp.reset()                                                                                      # :532
+    for i in range(chunks[0]):                                                                      # :534-537, per video
+        bp.step_train([x[i * chunk:(i + 1) * chunk] for x, c in zip(xs, chunks) if c > i], ragged=True)
+    caches = [bp.memory_cache(b) for b in range(k)]                          # per video, oldest first
+    counts = [len(c) for c in caches]
+    R = rm.num_memory_tokens * P
+    temb = model.token_type_embedding.weight
+    fuser = model.memory_fuser
+    if _ragged_fuser_rows(capi.lib(), counts, R, D, fuser[0].weight.shape[0]):
+        mem = torch.cat([m.reshape(R, D) for c in caches for m in c], dim=0)                        # :545, every video
+        fused = ag.fuser_mlp(fuser, mem, temb[0], fused_gelu=True)                                  # :546-553
+        at = [sum(counts[:b]) * R for b in range(k + 1)]
+        blocks = [fused[at[b]:at[b + 1]] for b in range(k)]
+    else:
+        # per ring slot (memory g of a video lives in slot g % cap), over the videos 0 .. h-1 that hold it
+        cap = int(getattr(rm.config, "cache_cap", 10))
+        place = [[None] * n for n in counts]
+        for sl in range(max(counts)):
+            hold = [b for b in range(k) if counts[b] > sl]
+            pos = [sl if chunks[b] <= cap else (sl - chunks[b] % cap + cap) % cap for b in hold]
+            out_sl = ag.fuser_mlp(fuser, torch.cat([caches[b][p].reshape(R, D) for b, p in zip(hold, pos)], dim=0), temb[0],
+                                  fused_gelu=True)
+            for j, (b, p) in enumerate(zip(hold, pos)):
+                place[b][p] = out_sl[j * R:(j + 1) * R]
+        blocks = [torch.cat(pl, dim=0) for pl in place]
+    _require_newline(image_newline, layout)
+    nl = None if layout == "no_token" else image_newline.to(device=dev, dtype=dt).reshape(1, D)
+    mp, fp = memory_prompt_embeds.to(dt), frame_prompt_embeds.to(dt)
+    toks = []
+    for b in range(k):
+        parts = [mp, _lay_out_block(blocks[b], nl, layout, P)]                                      # :567-634
+        if with_frames:
+            fine = xs[b][_device_indices(fines[b], dev)] + temb[1].to(dt)                           # :513-524,554
+            parts += [fp, _lay_out_block(fine.reshape(-1, D), nl, layout, P)]
+        toks.append(torch.cat(parts, dim=0))
+    back = [0] * k                               # caller's position -> position in the stepping order
+    for j, i in enumerate(order):
+        back[i] = j
+    info = {"order": order, "num_memories": [counts[back[i]] for i in range(k)],
+            "pe_frames": [xs[back[i]] for i in range(k)], "fine_idx": [fines[back[i]] for i in range(k)],
+            "block_rows": [toks[back[i]].shape[0] for i in range(k)], "frame_scores": bp.frame_scores}
+    return [toks[back[i]] for i in range(k)], info
 
 
 ROW_BATCH_SIZES = (8, 4, 2)
@@ -679,7 +771,7 @@ def features_per_sample(video_of, tokens):
 
 
 def run_video_groups(model, videos, mem_prompt, frame_prompt, image_newline, with_frames=True, layout="one_token",
-                     sizes=ROW_BATCH_SIZES, train=False, out=None, dst_rows=None, single=None, ragged=False):
+                     sizes=ROW_BATCH_SIZES, train=False, out=None, dst_rows=None, single=None, ragged=False, ragged_train=False):
     """The memory path for several videos on the current stream - the ONE place that groups videos into row batches.
     `videos`: (pooled frame tokens [T, P, D], original frame indices [T] on the host) per video.  Videos with the same sampled
     frame count, dtype and device form a group (they share chunk bounds and fine-frame indices); `plan_row_batches` cuts it into
@@ -691,10 +783,13 @@ def run_video_groups(model, videos, mem_prompt, frame_prompt, image_newline, wit
                        one emit per row batch (mavlm_fuse_emit_layout_batch_to), the `out=` slice for a single; returns None.
     `ragged` (LlavaMetaForCausalLM.enable_ragged_row_batches; inference - under autograd the grouping above stays): videos whose
     sampled length is a multiple of the 32-frame chunk are grouped by `plan_ragged_batches` instead - different chunk counts
-    in one row batch, one ragged emit per group (`video_memory_tokens_batched(ragged=True)`); the rest as above."""
+    in one row batch, one ragged emit per group (`video_memory_tokens_batched(ragged=True)`); the rest as above.
+    `ragged_train` (enable_ragged_row_batches(on, training=True)): with `train` the grouping comes from `plan_ragged_batches`
+    too (same policy, same sizes) and a group runs through `video_memory_tokens_ragged_train`; without `train` it
+    changes nothing."""
     rm = model.recurrent_memory_transformer
     groups = []
-    if ragged and not train:
+    if (ragged and not train) or (ragged_train and train):
         groups, batches, singles = plan_ragged_batches([v[0].shape[0] for v in videos], 32,
                                                        [(v[0].dtype, str(v[0].device)) for v in videos], sizes)
     else:
@@ -706,6 +801,12 @@ def run_video_groups(model, videos, mem_prompt, frame_prompt, image_newline, wit
     tokens = [None] * len(videos)
     for size, grp in groups:
         bp = rm.row_batcher(size)
+        if train:
+            toks = video_memory_tokens_ragged_train(model, bp, [videos[i][0] for i in grp], [videos[i][1] for i in grp],
+                                                    mem_prompt, frame_prompt, image_newline, with_frames, layout=layout)[0]
+            for j, i in enumerate(grp):
+                tokens[i] = toks[j]
+            continue
         toks = video_memory_tokens_batched(model, bp, [videos[i][0] for i in grp], [videos[i][1] for i in grp], mem_prompt,
                                            frame_prompt, image_newline, with_frames, out=out, layout=layout,
                                            dst_rows=None if out is None else [dst_rows[i] for i in grp], ragged=True)[0]
@@ -1140,7 +1241,8 @@ class LlavaMetaForCausalLM:
         train = path_wants_grad(model, mem_prompt, frame_prompt, newline)
         if train or plan.general or not vids[0][0].is_cuda or any(p.device != dev or p.dtype != dt for p, _ in vids):
             tokens = run_video_groups(model, vids, mem_prompt, frame_prompt, newline, not drop, layout, self.row_batch_sizes,
-                                      train=train, ragged=self._ragged_row_batches and not train)
+                                      train=train, ragged=self._ragged_row_batches and not train,
+                                      ragged_train=self._ragged_row_batches_train and train)
             return splice_into_text(self, model, features_per_sample(plan.video_of, tokens), input_ids, position_ids,
                                     attention_mask, past_key_values, labels)
         # in place: the padded buffer once, text rows from embed_tokens, padding zeroed, every block emitted where it belongs
@@ -1163,16 +1265,21 @@ class LlavaMetaForCausalLM:
         return None, _pos_skipping(self, out_pos, emb), out_mask, past_key_values, emb, out_labels
 
     _ragged_row_batches = False
+    _ragged_row_batches_train = False
 
-    def enable_ragged_row_batches(self, on: bool = True):
+    def enable_ragged_row_batches(self, on: bool = True, training: bool = False):
         """Several videos per forward: let a row batch hold videos of DIFFERENT lengths (off by default).  Off, videos step
         together only when their sampled frame counts are equal (`plan_row_batches`); everything else runs as single videos.
         On, every video whose sampled length is a multiple of the 32-frame chunk - the sampler turns every video of 32 or more
         frames into one - is grouped by `plan_ragged_batches`: up to 8 videos whose chunk counts differ by at most a factor of
         two share one row-batched engine, ordered longest first and stepped as a shrinking prefix, with one ragged emit per
         group into the padded `inputs_embeds`.  Inference; a forward that records a graph keeps the grouping of the switch off.
-        The hipGraph cache and `MemoryPathPool` are not affected."""
+        The hipGraph cache and `MemoryPathPool` are not affected.
+        `training=True` additionally groups the videos of a forward under autograd that way (off by default, also with `on`):
+        a group steps through `BatchedProjector.step_train(ragged=True)`, forward and backward of its active videos in one pass
+        per step; `on=False` switches both off."""
         self._ragged_row_batches = bool(on)
+        self._ragged_row_batches_train = bool(on) and bool(training)
 
     # -- hipGraph replay for repeated video shapes (round 4) -------------------------------------------------------------
     def enable_memory_graphs(self, capacity: int = 4):

@@ -705,6 +705,22 @@ class TransformerProjector(nn.Module):
         return self._memory_cache, self.frame_attn_scores
 
 
+def ragged_fifo_plan(steps, cap):
+    """FIFO bookkeeping of a ragged row batch under autograd (pure host helper).  `steps`: the steps each video has taken so far
+    (its chunk count once it is done) - all videos start together, so step t of the batch is step t of every video that takes
+    it; `cap`: the FIFO length.  Video b holds the memories of its OWN last min(steps[b], cap) steps, whatever the batch did
+    afterwards.  Returns (held, droppable): held[b] = the batch steps whose memory video b's FIFO holds, oldest first;
+    droppable = the steps below max(steps) that no video holds - the cached entries that may go.  Equal counts n give
+    held = [n - cap, n) for every video and droppable = [0, n - cap): the batch-wide trimming of the equal-length path."""
+    cap = int(cap)
+    steps = [int(c) for c in steps]
+    if cap < 1 or any(c < 0 for c in steps):
+        raise ValueError("ragged_fifo_plan: cap >= 1 and step counts >= 0")
+    held = [list(range(max(0, c - cap), c)) for c in steps]
+    keep = {t for h in held for t in h}
+    return held, [t for t in range(max(steps, default=0)) if t not in keep]
+
+
 class BatchedProjector:
     """B independent videos stepped TOGETHER over the parameters of one `TransformerProjector` (row batch).
 
@@ -732,7 +748,13 @@ class BatchedProjector:
     contraction over all videos' rows: fp32 accumulation, one rounding), forward and backward attention serve the B*heads
     (video, head) pairs in one launch each.  Its activations are bit-identical to `step`'s; `memory_cache(b)` then returns
     graph-carrying [M, P, D] tensors (BPTT through the un-detached FIFO, as the reference) and `frame_scores` the detached
-    [B, F] scores.  One video batch runs in one mode: `reset()` between `step` and `step_train`."""
+    [B, F] scores.  One video batch runs in one mode: `reset()` between `step` and `step_train`.
+
+    `step_train(segs, ragged=True)` is the ragged row batch under autograd: the chunk-count rule and the longest-first order of
+    `step`; a step over k active videos runs every operator with nb = k over the first k videos' rows (k >= 2: the launches of a
+    `BatchedProjector` of size k; k = 1: those of the single-video training step), and the frame scores of all k videos come from
+    ONE column-sum launch (`ops.attention_colsum_batch`).  The FIFO is per video (`ragged_fifo_plan`): a finished video keeps the
+    memories of its own last steps until `reset()`.  A batch is ragged or not from its first step on."""
 
     def __init__(self, proj: TransformerProjector, batch: int, fused_ln_never: bool = False):
         self.fused_ln_never = bool(fused_ln_never)
@@ -751,6 +773,9 @@ class BatchedProjector:
         self._mode = None                     # "engine" (step) / "autograd" (step_train) once a video batch has started
         self._tcache = []                     # training path: the cached memories, stacked [B*R, D] graph tensors, oldest first
         self._tevo = []                       # ... and their evolution K/V projections ([B, R, Dp] views), one pair per entry
+        self._tragged = None                  # training path: True / False once a batch has started ragged / not (`reset` clears)
+        self._tsteps = []                     # ragged training: the batch step of each `_tcache` entry ([k_t * R, D], k_t videos)
+        self._tevo_steps = []                 # ... and of each `_tevo` entry ([k, R, Dp] views, k = the videos of the step after)
 
     def engine(self, device, dtype, frames=None) -> _Engine:
         proj = self.proj
@@ -777,6 +802,7 @@ class BatchedProjector:
         self._vsteps = [0] * self.batch
         self._mode = None
         self._tcache, self._tevo = [], []
+        self._tragged, self._tsteps, self._tevo_steps = None, [], []
         if self._engine is not None:
             capi.check(capi.lib().mavlm_reset(self._engine.ctx), "mavlm_reset")
             if self.proj._weights_maybe_stale(self._packed_epoch):
@@ -825,10 +851,14 @@ class BatchedProjector:
             self.frame_scores.append(scores)
         return scores
 
-    def step_train(self, segs):
+    def step_train(self, segs, ragged=False):
         """One chunk of every video under autograd (see the class docstring): segs = B tensors [F, P, D] of one shape.  Mirrors
         `TransformerProjector._forward_autograd` over the stacked rows, in the launch order of `mavlm_step_batch`.  Returns the
-        detached [B, F] frame scores (None with `compute_frame_scores = False`)."""
+        detached [B, F] frame scores (None with `compute_frame_scores = False`).
+        `ragged=True`: the chunks of the first len(segs) videos - 2 .. B at the first step of a batch, afterwards 1 .. the count
+        of the step before (`_step_train_ragged`); returns [len(segs), F] scores."""
+        if ragged:
+            return self._step_train_ragged(segs)
         from ... import _autograd as ag
         proj, B = self.proj, self.batch
         if self.record_attention_maps:
@@ -847,7 +877,11 @@ class BatchedProjector:
         if self._mode == "engine":
             raise capi.MavlmError("BatchedProjector.step_train: this video batch was started by the inference `step`: `reset()` "
                                   "before running the training path")
+        if self._tragged:
+            raise capi.MavlmError("BatchedProjector.step_train: this video batch was started as a ragged row batch "
+                                  "(`ragged=True`): `reset()` before stepping it without the keyword")
         self._mode = "autograd"
+        self._tragged = False
         proj._train_state["epoch"] += 1          # an optimizer step may follow: packed copies are suspect afterwards
         dt = segs[0].dtype
         M = proj.num_memory_tokens
@@ -890,11 +924,100 @@ class BatchedProjector:
             self.frame_scores.append(scores)
         return scores
 
-    def _chunk_kv(self, ag, atts, segs, S, D):
+    def _step_train_ragged(self, segs):
+        """`step_train(ragged=True)`: one chunk of the first k = len(segs) videos (longest first; the prefix only shrinks).  Rows
+        [:k*R] of the newest cached memory and [:k] of the cached evolution K/V are the active videos'; a cached memory is
+        projected for the evolution over the rows of the videos that step again only."""
+        from ... import _autograd as ag
+        proj, B = self.proj, self.batch
+        k = len(segs)
+        if self.record_attention_maps:
+            raise capi.MavlmError("record_attention_maps is not supported on the autograd (training) path: attention maps are "
+                                  "recorded by inference steps only")
+        if self._mode == "engine":
+            raise capi.MavlmError("BatchedProjector.step_train: this video batch was started by the inference `step`: `reset()` "
+                                  "before running the training path")
+        if self._tragged is False:
+            raise capi.MavlmError("BatchedProjector.step_train(ragged=True): this video batch was started without the keyword: "
+                                  "`reset()` before stepping it as a ragged row batch")
+        if (self._active == 0 and not 2 <= k <= B) or (self._active and not 1 <= k <= self._active):
+            raise capi.MavlmError(f"BatchedProjector.step_train(ragged=True): 2..{B} chunks at the first step of a batch, then no "
+                                  f"more than the step before ({self._active or B}): the prefix of active videos never grows; "
+                                  f"got {k}")
+        if any(t.dim() != 3 for t in segs):
+            raise capi.MavlmError("BatchedProjector.step_train: [F, P, D] chunks expected")
+        F, P, D = segs[0].shape
+        for t in segs:
+            if not t.is_cuda or tuple(t.shape) != (F, P, D) or t.dtype != segs[0].dtype:
+                raise capi.MavlmError("BatchedProjector.step_train: GPU chunks of one shape / dtype expected")
+        if P != proj.patch_size or D != proj.hidden_size or F < 1:
+            raise capi.MavlmError(f"expected [F,{proj.patch_size},{proj.hidden_size}] chunks")
+        self._mode = "autograd"
+        self._tragged = True
+        proj._train_state["epoch"] += 1          # an optimizer step may follow: packed copies are suspect afterwards
+        dt = segs[0].dtype
+        R = proj.num_memory_tokens * P
+        S = F * P
+        cap = int(getattr(proj.config, "cache_cap", 10))
+        evo = proj.memory_update_attention
+        n = self._n                                                 # this step's index: the same for every video that takes it
+        if self._tcache:                                            # memory evolution (MemoryController.py:89-97, 125-127)
+            newest = self._tcache[-1][:k * R]                       # (step n - 1: video 0 holds it)
+            kv = ag.project_kv([evo], newest, nb=k)[0]              # one packed GEMM over the rows of the videos that step again
+            self._tevo.append(kv if k > 1 else (kv[0].unsqueeze(0), kv[1].unsqueeze(0)))
+            self._tevo_steps.append(n - 1)
+            # keys of a video in the slot order of the inference ring (memory g lives in slot g % cap)
+            order = sorted(range(len(self._tevo)), key=lambda i: self._tevo_steps[i] % cap)
+            kk = torch.cat([self._tevo[i][0][:k] for i in order], dim=1)               # [k, n*R, Dp]
+            vv = torch.cat([self._tevo[i][1][:k] for i in order], dim=1)
+            if k == 1:
+                kk, vv = kk[0], vv[0]
+            m, _ = ag.attention_block(evo, newest, kk, vv, nb=k)
+        else:
+            self._tevo, self._tevo_steps = [], []
+            m = (proj.initial_memory + proj.memory_pos_embed).to(dt).reshape(R, D).repeat(k, 1)      # :123-124, every video
+        atts = [layer.memory_segment_fusion_attention for layer in proj.layers]
+        kvs = self._chunk_kv(ag, atts, segs, S, D, nb=k)
+        stats = None
+        for li, layer in enumerate(proj.layers):                    # memory formation (:132-133)
+            last_layer = li == len(proj.layers) - 1
+            a, stats = ag.attention_block(atts[li], m, kvs[li][0], kvs[li][1], want_stats=last_layer and self.compute_frame_scores,
+                                          patches_per_frame=P, nb=k)
+            m = ag.mlp_block(layer, a)
+        self._tcache.append(m)                                      # :152
+        self._tsteps.append(n)
+        self._n += 1
+        self._active = k
+        for b in range(k):
+            self._vsteps[b] += 1
+        # per-video FIFO: an entry goes once no video - finished ones included - holds its step; the evolution reads the active
+        # videos' last `cap` steps only
+        _, gone = ragged_fifo_plan(self._vsteps, cap)
+        if gone:
+            keep = [i for i, t in enumerate(self._tsteps) if t not in set(gone)]
+            self._tcache, self._tsteps = [self._tcache[i] for i in keep], [self._tsteps[i] for i in keep]
+        while self._tevo_steps and self._tevo_steps[0] <= self._n - cap - 1:
+            self._tevo, self._tevo_steps = self._tevo[1:], self._tevo_steps[1:]
+        scores = None
+        if stats is not None:                                       # :135-139, 156 (detached statistics)
+            with torch.no_grad():
+                q, kl, lse = stats
+                H, hd = atts[-1].num_attention_heads, atts[-1].attention_head_size
+                part = ops.attention_colsum_batch(q, kl if k > 1 else kl.unsqueeze(0), lse, H, k, head_dim=128 if hd <= 128 else hd,
+                                                  scale=ops.attn_scale(hd))
+                # (finished per video with the single-video path's torch ops on its [H, S] plane: the same bits)
+                scores = torch.stack([part[b].sum(dim=0).view(F, P).mean(dim=1).to(dt) for b in range(k)])
+            self.frame_scores.append(scores)
+        return scores
+
+    def _chunk_kv(self, ag, atts, segs, S, D, nb=None):
         """K/V of the chunk for all layers as [B, S, W] views: ONE GEMM over the stacked frames where that gives the bits of the
         step's per-video GEMMs (row-independent kernels; only a split contraction - `mavlm_linear_ws_floats`, a function of
-        the row count - sums in another order), else one GEMM per video as the step runs them."""
-        B = self.batch
+        the row count - sums in another order), else one GEMM per video as the step runs them.  `nb`: the videos of a ragged
+        step (default: the whole batch); one video gives the single-video step's [S, W] views."""
+        B = self.batch if nb is None else nb
+        if B == 1:
+            return ag.project_kv(atts, segs[0].detach().reshape(S, D))
         frames = [t.detach().reshape(S, D) for t in segs]           # frame features carry no gradient (llava_arch.py:302)
         a0 = atts[0]
         N = 2 * len(atts) * a0.num_attention_heads * ag.head_width(a0.attention_head_size)
@@ -922,6 +1045,10 @@ class BatchedProjector:
         [M, P, D] tensors after `step_train`"""
         if self._mode == "autograd":
             proj = self.proj
+            if self._tragged:                # video b's own last steps: entry t holds the rows of the k_t videos of step t
+                held = set(ragged_fifo_plan(self._vsteps, int(getattr(proj.config, "cache_cap", 10)))[0][b])
+                return [m.view(-1, proj.num_memory_tokens, proj.patch_size, proj.hidden_size)[b]
+                        for m, t in zip(self._tcache, self._tsteps) if t in held]
             return [m.view(self.batch, proj.num_memory_tokens, proj.patch_size, proj.hidden_size)[b] for m in self._tcache]
         eng = self._engine
         cap = eng.c.cache_cap

@@ -3,7 +3,11 @@ backward, 64 frames, M=64, D=1024, bf16 - wall time and per-kernel-kind breakdow
 usage: python tools/bench_train.py [steps]
 env: MEM_TOKENS, HIDDEN, BWD_FUSED; BATCH=B (default 1: the single-video path, the output below) or a list "1,2,4,8": the
 row-batched training step (BatchedProjector.step_train) of B distinct videos against the single-video step, the configurations
-interleaved round by round in this one process; ms per step and per video, then the kernel table of each."""
+interleaved round by round in this one process; ms per step and per video, then the kernel table of each.
+CHUNKS=3,2,2,1: videos of that many 32-frame chunks each, timed three ways, interleaved round by round in this one process: as ONE
+ragged row batch (step_train(ragged=True) on the smallest engine of 2 / 4 / 8 that holds them), under the equal-length grouping
+(plan_row_batches over the chunk counts: row batches of equal length plus single videos) and as single videos; ms per pass and per
+(video, chunk) step, then the kernel table - launches per pass - of each."""
 import ctypes, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -52,6 +56,63 @@ def kernel_table(fn):
                   + (f"  {fl[i]/(ms[i]*1e-3)/1e12:7.1f} TF" if fl[i] else f"  {by[i]/(ms[i]*1e-3)/1e9:7.1f} GB/s"))
     print(f"sum of HIP kernels {tot/steps:.2f} ms/step (torch glue kernels not included)")
     return tot / steps
+
+if os.environ.get("CHUNKS"):
+    from memory_augmented_vlm_amd.model import llava_arch as arch
+    from memory_augmented_vlm_amd.model.memory_module.MemoryController import BatchedProjector
+    counts = sorted((int(v) for v in os.environ["CHUNKS"].split(",")), reverse=True)          # longest first
+    vids = [(torch.randn(32 * n, 196, HID, device="cuda") * 0.5).bfloat16() for n in counts]   # distinct videos
+    loss_of = lambda mems: sum(cm.float().square().mean() for cm in mems)
+    def single_video(v):
+        rm.memory_cache = []
+        for i in range(v.shape[0] // 32):
+            cache, _ = rm(v[32 * i:32 * i + 32])
+        return loss_of(cache)
+    def singles():
+        rm.zero_grad(set_to_none=True)
+        sum(single_video(v) for v in vids).backward()
+    batches, alone = arch.plan_row_batches(counts)
+    bps = {len(g): BatchedProjector(rm, len(g)) for g in batches}
+    def grouped():
+        rm.zero_grad(set_to_none=True)
+        loss = 0.0
+        for g in batches:
+            bp = bps[len(g)]
+            bp.reset()
+            for i in range(counts[g[0]]):
+                bp.step_train([vids[j][32 * i:32 * i + 32] for j in g])
+            loss = loss + sum(loss_of(bp.memory_cache(b)) for b in range(len(g)))
+        for j in alone:
+            loss = loss + single_video(vids[j])
+        loss.backward()
+    rbp = BatchedProjector(rm, next(sz for sz in (2, 4, 8) if sz >= len(counts)))
+    def ragged():
+        rm.zero_grad(set_to_none=True)
+        rbp.reset()
+        for i in range(counts[0]):
+            rbp.step_train([v[32 * i:32 * i + 32] for v, n in zip(vids, counts) if n > i], ragged=True)
+        sum(loss_of(rbp.memory_cache(b)) for b in range(len(counts))).backward()
+    fns = {"ragged": ragged, "grouped": grouped, "singles": singles}
+    print(f"CHUNKS={counts}  M={M} hidden={HID}; equal-length grouping: row batches {[[counts[j] for j in g] for g in batches]}, "
+          f"single videos {[counts[j] for j in alone]}")
+    for fn in fns.values():
+        for _ in range(2): fn()
+    times = {k: [] for k in fns}
+    for _ in range(int(os.environ.get("ROUNDS", "3"))):
+        for k, fn in fns.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(steps): fn()
+            torch.cuda.synchronize(); times[k].append((time.perf_counter() - t0) / steps)
+    for k in fns:
+        t = sorted(times[k])
+        print(f"{k:8s}: fwd+bwd of all videos median {t[len(t)//2]*1e3:.2f} ms  min {t[0]*1e3:.2f}  max {t[-1]*1e3:.2f}   "
+              f"per (video, chunk) step {t[len(t)//2]*1e3/sum(counts):.2f} ms   (rounds {['%.2f' % (v*1e3) for v in times[k]]})")
+    print(f"peak mem {torch.cuda.max_memory_allocated()/2**30:.2f} GiB")
+    if os.environ.get("TABLES", "1") != "0":
+        for k, fn in fns.items():
+            print(f"---- kernel kinds, {k} (per pass over all videos: {sum(counts)} (video, chunk) steps, {counts[0]} batch steps)")
+            kernel_table(fn)
+    sys.exit(0)
 
 if BATCHES != [1]:
     from memory_augmented_vlm_amd.model.memory_module.MemoryController import BatchedProjector
