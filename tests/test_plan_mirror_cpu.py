@@ -101,6 +101,109 @@ def test_wide_head_plans_match_the_oracle(lib):
         assert lib.mavlm_attention_hd_ws_floats(R, S, H, 256) == (ns * (R * H * 256 + H * R) if ns > 1 else 0), (R, S, H)
 
 
+@pytest.fixture
+def level_hooks(lib, monkeypatch, request):
+    """set the stream-K hooks of the library and their mirrors in the oracle together; both are restored afterwards"""
+    request.addfinalizer(lambda: (lib.mavlm_set_attention_streamk_min_tiles(64), lib.mavlm_set_attention_streamk_waves(0)))
+
+    def set_hooks(min_tiles, waves):
+        capi.check(lib.mavlm_set_attention_streamk_min_tiles(min_tiles), "min tiles")
+        capi.check(lib.mavlm_set_attention_streamk_waves(waves), "waves")
+        monkeypatch.setattr(O, "STREAMK_MIN_TILES", min_tiles)
+        monkeypatch.setattr(O, "STREAMK_WAVES", waves)
+    return set_hooks
+
+
+def _narrow_plan_equals(lib, R, S, H, waves, G, full, levels):
+    """head_dim 128: C plan and oracle against the literal (G, whole rounds, levels); the unit map is a bijection"""
+    info = (ctypes.c_int32 * 4)()
+    capi.check(lib.mavlm_attention_plan(R, S, H, info), "plan")
+    QB = 32 * waves
+    assert list(info) == [waves, G, len(levels), 1], (R, S, H, list(info))
+    assert O.streamk_plan(R, S, H) == (G, QB, full, levels), (R, S, H, O.streamk_plan(R, S, H))
+    assert lib.mavlm_attention_plan_unit(R, S, H, -1, full - 1, 0) >= 0 and lib.mavlm_attention_plan_unit(R, S, H, -1, full, 0) == -1
+    assert lib.mavlm_attention_plan_unit(R, S, H, len(levels), 0, 0) == -1
+    seen = [lib.mavlm_attention_plan_unit(R, S, H, -1, si, v) for si in range(full) for v in range(G)]
+    for lv, (k, base, n) in enumerate(levels):
+        assert lib.mavlm_attention_plan_unit(R, S, H, lv, 0, n) == -1, (R, S, H, lv)
+        for ul in range(n):
+            u = lib.mavlm_attention_plan_unit(R, S, H, lv, 0, ul)
+            assert u == O.streamk_unit_of_level(G, full, levels, lv, ul), (R, S, H, lv, ul)
+            seen.append(u)
+    assert sorted(seen) == list(range(-(-R // QB) * H)), (R, S, H)
+    assert lib.mavlm_attention_ws_floats(R, S, H) == G * len(levels) * (QB * 128 + QB), (R, S, H)
+
+
+def _wide_plan_equals(lib, R, S, H, G, full, levels):
+    info = (ctypes.c_int32 * 4)()
+    capi.check(lib.mavlm_attention_hd_plan_info(R, S, H, 448, info), "plan info")
+    assert list(info) == [G, full, len(levels), 1], (R, S, H, list(info))
+    assert O.streamk_plan_wide(R, S, H) == (G, full, levels), (R, S, H, O.streamk_plan_wide(R, S, H))
+    cuts = O.streamk_split_tiles_wide(R, S, H)
+    nqb = -(-R // 128)
+    # position order: the whole rounds take the first full * G units, the levels the rest, each unit once
+    assert sorted(h * nqb + b for h, b in cuts) == list(range(full * G, nqb * H)), (R, S, H)
+    assert lib.mavlm_attention_hd_ws_floats(R, S, H, 448) == G * len(levels) * (128 * 448 + 128), (R, S, H)
+
+
+def test_streamk_level_cases_are_what_the_library_plans(lib, level_hooks):
+    """The table of tests/streamk_cases.py - the plans the GPU tests of the cut levels launch - against the C library and the
+    oracle under the same hooks: G, whole rounds, the level list, the unit bijection; and the table's coverage: every cut width the
+    plan rule can produce, a plan of at least four levels and one with two or more whole rounds per kernel."""
+    import streamk_cases as T
+    for kernel, R, S, H, G, full, levels in T.STREAMK_CASES:
+        level_hooks(T.MIN_TILES, T.WAVES[kernel])
+        if kernel == "wide":
+            _wide_plan_equals(lib, R, S, H, G, full, levels)
+        else:
+            _narrow_plan_equals(lib, R, S, H, T.WAVES[kernel], G, full, levels)
+    level_hooks(T.MIN_TILES, 0)
+    for kernel, nb, R, S, H, G, full, levels in T.BATCH_CASES:
+        nqb = -(-R // (128 if kernel == "wide" else 256))
+        if kernel == "wide":
+            _wide_plan_equals(lib, R, S, H, G, full, levels)
+            cut = {h * nqb + b for h, b in O.streamk_split_tiles_wide(R, S, H)}
+            assert lib.mavlm_attention_batch_ws_floats(R, S, H, nb, 448) == lib.mavlm_attention_hd_ws_floats(R, S, H, 448)
+        else:
+            _narrow_plan_equals(lib, R, S, H, 8, G, full, levels)
+            cut = {lib.mavlm_attention_plan_unit(R, S, H, lv, 0, ul) for lv, (_, _, n) in enumerate(levels) for ul in range(n)}
+            assert lib.mavlm_attention_batch_ws_floats(R, S, H, nb, 128) == lib.mavlm_attention_ws_floats(R, S, H)
+        videos = {u // nqb // (H // nb) for u in cut}
+        # the XCD-affine order of head_dim 128 deals cut units to every video; the position order of the wide kernel cuts the
+        # tail of the head-major order, which reaches back over a video boundary only from three videos on
+        assert videos == (set(range(nb)) if kernel != "wide" else ({1} if nb == 2 else {1, 2})), (kernel, nb, videos)
+    for kernel, want in (("w8", {1, 2, 3, 4, 5}), ("w4", {2, 3, 4, 5}), ("wide", {1, 2, 3, 4, 5})):
+        mine = T.cases_of(kernel)
+        assert {k for c in mine for k, _, _ in c[6]} == want, kernel
+        assert max(len(c[6]) for c in mine) >= 4 and max(c[5] for c in mine) >= 2, kernel
+        assert any(c[1] % (32 * (T.WAVES[kernel] or 4)) and len(c[6]) > 1 for c in mine), kernel       # ragged and multi-level
+        assert any(-(-c[2] // (32 if kernel == "wide" else 64)) < 32 and c[6][-1][0] == 5 for c in mine), kernel   # empty pieces
+
+
+def test_split_kv_cases_cover_every_plane_count(lib):
+    """The split-KV shapes of tests/streamk_cases.py under the default hooks: the C plans and the oracle give the listed plane
+    counts, which cover 2 .. 8 at head_dim 128 and 2 .. 7 (the most the wide plan gives over a sweep) at 448, each at least once
+    with a ragged last key tile and a short last plane."""
+    import streamk_cases as T
+    info = (ctypes.c_int32 * 4)()
+    ragged = {128: set(), 448: set()}
+    for R, S, H, n128, n448 in T.SPLIT_CASES:
+        if n128 is not None:
+            capi.check(lib.mavlm_attention_plan(R, S, H, info), "plan")
+            ns, tps = O.split_plan(R, S, H)
+            assert info[1] == 0 and info[3] == n128 == ns, (R, S, H, list(info), ns)
+            if S % 64 and -(-S // 64) % tps:
+                ragged[128].add(ns)
+        if n448 is not None:
+            capi.check(lib.mavlm_attention_hd_plan_info(R, S, H, 448, info), "plan info")
+            ns, tps = O.split_plan_wide(R, S, H)
+            assert info[0] == 0 and info[3] == n448 == ns, (R, S, H, list(info), ns)
+            if S % 32 and -(-S // 32) % tps:
+                ragged[448].add(ns)
+    assert ragged[128] == set(range(2, 9)) and ragged[448] == set(range(2, 8)), ragged
+    assert max(O.split_plan_wide(R, S, H)[0] for R, S, H in itertools.product(ROWS, KEYS, [1, 2, 3, 8, 32])) == 7
+
+
 def test_frame_score_rule_matches_the_oracle(lib):
     for R, H, P in itertools.product(ROWS, HEADS, [4, 60, 64, 100, 196, 198]):
         for F in (1, 2, 3, 32, 40, 64, 65):
