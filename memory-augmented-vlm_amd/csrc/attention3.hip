@@ -45,6 +45,13 @@ __device__ __forceinline__ int img3_x(int row) { return ((row & 3) << 2) | ((row
 template <int V>
 struct IC { static constexpr int value = V; };
 
+// x c - mc with the product rounded before the subtraction (never contracted into an fma)
+__device__ __forceinline__ float mul_sub_2r(float x, float c, float mc) {
+#pragma clang fp contract(off)
+  const float p = x * c;
+  return p - mc;
+}
+
 // A workgroup runs one or more SEGMENTS.  A segment = one unit (head h, 128-query block) x a contiguous range of its key
 // tiles, computed with a fresh online-softmax state; a segment that covers all key tiles of its unit writes O / lse2, any
 // other writes a NORMALISED fp32 partial + its log-sum-exp for a merge kernel.  Three schedules (plan.wgs / tps):
@@ -416,10 +423,16 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
   max_and_rescale(IC<0>{});
 
   // ---- one pipelined iteration: S in st[P] (tile t, reference m_run already decided), S' of tile t+1 into st[P^1]
-  auto iteration = [&](auto par, int t) {
+  // STEADY (compile-time): tile t + 1 exists and is not the ragged last tile - the loop below runs this form while that holds
+  // for both tiles of a pair.  `has_next` is then a constant and no mask_tail code is compiled in: [A] and [B] are one basic
+  // block each, with their vector work in the MFMA gaps.  (With a run-time `has_next` the 16 conditional v_max3 of [B] cut
+  // the chain into 16 blocks and the compiler sank all 32 row-sum adds behind the last MFMA as one dependent chain - on every
+  // odd tile, where `t + 2 < nt` is not known.)  The run-time form finishes the last one to three tiles of a segment.
+  auto iteration = [&](auto par, auto steady, int t) {
     constexpr int P = decltype(par)::value;
     constexpr int N = P ^ 1;
-    const bool has_next = t + 1 < nt;
+    constexpr bool STEADY = decltype(steady)::value != 0;
+    const bool has_next = STEADY || t + 1 < nt;
     const int ktile = (t + 2) * KT3 * ldk * 2, vtile = (t + 1) * KT3 * ldv * 2;     // scalar byte offsets of K(t+2), V(t+1)
     // K(t+2) -> K slot (t&1) == P ; V(t+1) -> V slot N.  Both slots were last read before the previous barrier.  The
     // eight DMA pieces are issued ONE PER TWO MFMA STEPS of phase A, not as a burst at the top: the vector-memory path of
@@ -478,10 +491,15 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
         constexpr int e0 = 2 * i, e1 = 2 * i + 1;             // elements (b = e>>4, idx = e&15) of tile t
         // The two empty asm statements are ordered against sched_barrier (both have side effects); the pure
         // fma/exp between them cannot be hoisted in front of the MFMA chain or sunk behind it.
+        // s c - m c is ONE fma everywhere, except for element 0 of an even tile that has a successor: that one has been a
+        // multiply and a subtract (two roundings) in every build of this loop - written as `x0 * c - mc`, the compiler
+        // paired x0 * c with m_run * c instead of contracting it.  Both forms are written out, so that the bits do not
+        // depend on such a choice (the form without a successor, below, has always been one fma per element).
         float x0 = st[P][e0 >> 4][e0 & 15], x1 = st[P][e1 >> 4][e1 & 15];
         asm volatile("" : "+v"(x0), "+v"(x1));
-        x0 = __builtin_amdgcn_exp2f(x0 * c - mc);
-        x1 = __builtin_amdgcn_exp2f(x1 * c - mc);
+        if constexpr (P == 0 && i == 0) x0 = __builtin_amdgcn_exp2f(mul_sub_2r(x0, c, mc));
+        else x0 = __builtin_amdgcn_exp2f(__builtin_fmaf(x0, c, -mc));
+        x1 = __builtin_amdgcn_exp2f(__builtin_fmaf(x1, c, -mc));
         asm volatile("" : "+v"(x0), "+v"(x1));
         st[P][e0 >> 4][e0 & 15] = x0;
         st[P][e1 >> 4][e1 & 15] = x1;
@@ -494,11 +512,12 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
 #pragma unroll
       for (int b = 0; b < 2; ++b)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) st[P][b][i] = __builtin_amdgcn_exp2f(st[P][b][i] * c - mc);
+        for (int i = 0; i < 16; ++i) st[P][b][i] = __builtin_amdgcn_exp2f(__builtin_fmaf(st[P][b][i], c, -mc));
     }
 
     // [B] O^T += V(t)^T.P(t)^T  ||  16-bit converts + row sums of tile t, row maximum of tile t+1
-    if (has_next && t + 1 == nt - 1 && (S & (KT3 - 1))) mask_tail(IC<N>{}, t + 1);
+    if constexpr (!STEADY)
+      if (has_next && t + 1 == nt - 1 && (S & (KT3 - 1))) mask_tail(IC<N>{}, t + 1);
     float psum = 0.f;
     float mx = has_next ? st[N][0][0] : 0.f;
     {
@@ -579,19 +598,21 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
       const bool cut = kofs <= KT3;                           // the frame ends inside this tile (or at its end)
       if (cut) {
         // as FR = 1 below: only the 32-key block that holds the boundary is looked at
+        int hz = hh;                                          // (opaque, as below)
+        asm volatile("" : "+v"(hz));
         if (kofs <= 32) {
           plo = 0.f;
 #pragma unroll
           for (int g4 = 0; g4 < 4; ++g4) {
             const float s4 = (st[P][0][4 * g4] + st[P][0][4 * g4 + 1]) + (st[P][0][4 * g4 + 2] + st[P][0][4 * g4 + 3]);
-            plo += (8 * g4 + 4 * hh < kofs) ? s4 : 0.f;
+            plo += (8 * g4 + 4 * hz < kofs) ? s4 : 0.f;
           }
           phi = fmaxf(psum - plo, 0.f);
         } else {
 #pragma unroll
           for (int g4 = 0; g4 < 4; ++g4) {
             const float s4 = (st[P][1][4 * g4] + st[P][1][4 * g4 + 1]) + (st[P][1][4 * g4 + 2] + st[P][1][4 * g4 + 3]);
-            phi += (32 + 8 * g4 + 4 * hh >= kofs) ? s4 : 0.f;
+            phi += (32 + 8 * g4 + 4 * hz >= kofs) ? s4 : 0.f;
           }
           plo = fmaxf(psum - phi, 0.f);
         }
@@ -613,6 +634,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
       if (f_end <= k_end) {                                   // the current frame ends inside (or at the end of) this tile
         flushed = true;
         const int kofs = f_end - t * KT3;                     // keys [0, kofs) of the tile belong to it: 4 <= kofs <= 64
+        int hz = hh;                                          // (opaque: the eight lane constants 8 g4 + 4 hh below are built
+        asm volatile("" : "+v"(hz));                          //  here - hoisted out of the kernel's loops they were spilled)
         // plo = this lane's mass of the keys below the boundary.  Only the 32-key block that holds the boundary is
         // looked at (4 of the lane's 8 four-key groups: keys 32 b + 8 g4 + 4 hh + 0..3); the other block is wholly on
         // one side and comes out of psum.
@@ -622,14 +645,14 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
 #pragma unroll
           for (int g4 = 0; g4 < 4; ++g4) {
             const float s4 = (st[P][0][4 * g4] + st[P][0][4 * g4 + 1]) + (st[P][0][4 * g4 + 2] + st[P][0][4 * g4 + 3]);
-            plo += (8 * g4 + 4 * hh < kofs) ? s4 : 0.f;
+            plo += (8 * g4 + 4 * hz < kofs) ? s4 : 0.f;
           }
         } else {                                              // boundary in block 1: psum minus its groups at / above it
           float phi = 0.f;
 #pragma unroll
           for (int g4 = 0; g4 < 4; ++g4) {
             const float s4 = (st[P][1][4 * g4] + st[P][1][4 * g4 + 1]) + (st[P][1][4 * g4 + 2] + st[P][1][4 * g4 + 3]);
-            phi += (32 + 8 * g4 + 4 * hh >= kofs) ? s4 : 0.f;
+            phi += (32 + 8 * g4 + 4 * hz >= kofs) ? s4 : 0.f;
           }
           plo = psum - phi;
         }
@@ -677,12 +700,20 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
     asm volatile("" ::: "memory");
   };
 
+  // Steady state while tile t + 2 exists and is not the last one (only the last tile can be ragged): both tiles of the pair
+  // then have a full, unmasked successor.  The last two or three tiles (one, if there is only one) run the run-time form.
   int t = 0;
-  for (; t + 1 < nt; t += 2) {
-    iteration(IC<0>{}, t);
-    iteration(IC<1>{}, t + 1);
+  for (; t + 3 < nt; t += 2) {
+    iteration(IC<0>{}, IC<1>{}, t);
+    iteration(IC<1>{}, IC<1>{}, t + 1);
   }
-  if (t < nt) iteration(IC<0>{}, t);
+  // (straight-line, not a second loop: as a loop of two bodies the tail cost 6-30 more spilled scalar registers than before)
+  // (t < nt here: every schedule hands a segment at least one tile - the prologue above has already computed S(0))
+  iteration(IC<0>{}, IC<0>{}, t);
+  if (t + 1 < nt) {
+    iteration(IC<1>{}, IC<0>{}, t + 1);
+    if (t + 2 < nt) iteration(IC<0>{}, IC<0>{}, t + 2);
+  }
 
   if constexpr (FR == 1 || FR == 3) {
     // a piece that ends inside a frame: the mass of that frame's keys seen so far is still in a_cur (whole units end on a
