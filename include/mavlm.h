@@ -176,6 +176,23 @@ int mavlm_step_batch(mavlm_ctx* ctx, const void* const* segs, int32_t F, void* f
  * the largest need over 1 .. B videos, behind the regions a context stepped with n_active = B uses (none of those moves). */
 int mavlm_step_batch_active(mavlm_ctx* ctx, const void* const* segs, int32_t n_active, int32_t F, void* frame_scores,
                             int32_t scores_f32, void* stream);
+/* Clip row batch: mavlm_step_batch_active where video b's chunk is [F[b], P, D], 1 <= F[b] <= max_chunk_frames (the videos of
+ * fewer than 32 frames, whose single chunk holds all their frames: llava_arch.py:436 steps each alone).  F = HOST array of
+ * n_active entries, read during the call.  The same prefix rule (n_active never grows after mavlm_reset); valid at any step -
+ * the evolution does not depend on F.  frame_scores: null, or video b's F[b] scores land at frame_scores + b * ld_scores
+ * (elements; ld_scores >= max F[b]); the entries behind them are not touched.
+ * All F equal and ld_scores == F[0] (or no scores): this IS mavlm_step_batch_active - the same launches, the same bits.
+ * Otherwise the step is the row-batch step of n_active videos - the same GEMM shapes and plans, the same fused / two-kernel
+ * LayerNorm choice - except: the chunk K/V GEMMs write the videos' keys back to back into the chunk K/V region; every formation
+ * layer runs the variable-length forward (mavlm_attention_batch_varlen: plain grid, a video's rows carry the bits of the
+ * plain-grid forward over its own keys; head_dim 448: one plain-grid launch per video); the frame scores come from the
+ * variable-length column sums (mavlm_attention_colsum_batch_varlen; 448: the per-video pass) and the finishing kernel, never from
+ * the forward - the memory is the same bits with and without frame_scores and under every mavlm_set_frame_score_mode.  The
+ * column sums of all videos use a scratch region of their own behind every other one (no offset of mavlm_workspace_layout moves).
+ * MAVLM_E_ARG: n_active outside 1 .. B, n_active > 16 with unequal F, an F[b] outside its range, ld_scores too small;
+ * MAVLM_E_STATE: a single-video context, a growing prefix, attention maps bound while the F differ. */
+int mavlm_step_batch_frames(mavlm_ctx* ctx, const void* const* segs, const int32_t* F, int32_t n_active, void* frame_scores,
+                            int64_t ld_scores, int32_t scores_f32, void* stream);
 /* steps video b of the context has taken since mavlm_reset (single video: b = 0).  mavlm_cache_len / mavlm_newest_slot /
  * mavlm_steps count the context's steps, which are video 0's.  MAVLM_E_ARG: b outside 0 .. B-1. */
 int mavlm_video_steps(const mavlm_ctx* ctx, int32_t b);
@@ -283,6 +300,18 @@ int mavlm_fuse_emit_layout_ragged_to(mavlm_ctx* ctx, int32_t n_videos, const voi
                                      int32_t n_fine, const void* mem_prompt, int32_t n_mem_prompt, const void* frame_prompt,
                                      int32_t n_frame_prompt, const void* newline, int32_t with_frames, int32_t layout, void* out,
                                      int64_t out_rows, const int64_t* dst_row, int64_t* rows, void* stream);
+/* mavlm_fuse_emit_layout_ragged_to with a fine-frame count per video (the emit behind mavlm_step_batch_frames: a clip of n frames
+ * has n fine frames): n_fine = HOST array of n_videos counts, fine_idx = DEVICE array [n_videos, fine_ld] - video b's n_fine[b]
+ * indices start b * fine_ld entries into it (fine_ld >= every n_fine[b]).  rows[b] = mavlm_layout_rows(cfg, n_b, n_fine[b], ...).
+ * The same code: mavlm_fuse_emit_layout_ragged_to is this call with a constant count and fine_ld = n_fine (the same launches, the
+ * same bits); with different counts the literal rows and the fine frames run once per range of consecutive videos with one
+ * count.  The bounds and disjointness checks are made by each block's own length, before anything is enqueued.  MAVLM_E_SHAPE:
+ * a hidden size that is no multiple of 256 (the row map of the fuser's second GEMM; refused here before anything is enqueued). */
+int mavlm_fuse_emit_layout_frames_to(mavlm_ctx* ctx, int32_t n_videos, const void* const* x_pe, const int64_t* fine_idx,
+                                     int64_t fine_ld, const int32_t* n_fine, const void* mem_prompt, int32_t n_mem_prompt,
+                                     const void* frame_prompt, int32_t n_frame_prompt, const void* newline, int32_t with_frames,
+                                     int32_t layout, void* out, int64_t out_rows, const int64_t* dst_row, int64_t* rows,
+                                     void* stream);
 /* Host only: rows of the token block of a video with n_memories cached memories and n_fine fine frames in a layout - the
  * sequence length the concat of llava_arch.py:722-731 ends up with after :567-634.  <0: MAVLM_E_ARG (bad config / counts /
  * layout), MAVLM_E_SHAPE (_GRID: patches is not a square). */
@@ -395,6 +424,17 @@ int64_t mavlm_attention_batch_ws_floats(int32_t R, int32_t S, int32_t H, int32_t
 int mavlm_attention_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, void* O,
                           int32_t ldo, float* lse2, int32_t R, int32_t S, int32_t H, float scale, float* ws,
                           int64_t ws_floats, int32_t nb, int64_t kv_bstride, int32_t head_dim, int32_t dtype, void* stream);
+/* mavlm_attention_batch with per-video key counts (heads of <= 128 columns): video b attends to its own S[b] >= 1 keys, which
+ * start kv_off[b] elements into K and V.  S and kv_off are HOST arrays of nb <= 16 entries, read during the call (they reach the
+ * kernel by value: no allocation, no copy, no synchronisation).  H counts the heads of ALL videos, lse2 is [H, R], Q / O hold
+ * the nb x R query rows video after video - as in mavlm_attention_batch.  Always the plain grid (one workgroup per video, head
+ * and 128-query block; no stream-K, no split-KV, no workspace): video b's rows of O and lse2 equal, bit for bit, mavlm_attention
+ * on that video's own operands.  All arguments are checked before anything is enqueued: MAVLM_E_ARG for a null pointer, nb < 1,
+ * nb > 16, H % nb != 0, S[b] < 1, kv_off[b] < 0 or not a multiple of 8, key ranges [kv_off[b], kv_off[b] + S[b] * ld) that
+ * overlap (by ldk or by ldv), bad strides; MAVLM_E_SHAPE for head_dim > 128 (448 included: one mavlm_attention_hd per video). */
+int mavlm_attention_batch_varlen(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, void* O,
+                                 int32_t ldo, float* lse2, int32_t R, const int32_t* S, const int64_t* kv_off, int32_t H,
+                                 float scale, int32_t nb, int32_t head_dim, int32_t dtype, void* stream);
 int mavlm_attention_colsum_hd(const void* Q, int32_t ldq, const void* K, int32_t ldk, const float* lse2, float* part,
                               int32_t R, int32_t S, int32_t H, int32_t head_dim, float scale, int32_t dtype, void* stream);
 /* part[H,S] fp32 = column sums over queries of the normalised probabilities.  MemoryController.py:135
@@ -420,6 +460,18 @@ int64_t mavlm_attention_colsum_batch_floats(int32_t R, int32_t S, int32_t H, int
 int mavlm_attention_colsum_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk, int64_t kv_bstride, const float* lse2,
                                  float* part, int64_t part_floats, int32_t R, int32_t S, int32_t H, int32_t nb, int32_t head_dim,
                                  float scale, int32_t dtype, void* stream);
+/* mavlm_attention_colsum_batch with per-video key counts (heads of <= 128 columns): S and kv_off are HOST arrays of nb <= 16
+ * entries, read during the call; video b's S[b] keys start kv_off[b] elements into K.  Every video runs the single-video
+ * schedule of its own (R, S[b], H) - workgroups and planes differ per video; the launch takes the largest grid and the surplus
+ * workgroups of a shorter video leave at once.  Video b's [H, S[b]] result starts sum_{a<b} mavlm_attention_colsum_floats(R, S[a], H)
+ * floats into `part` and equals mavlm_attention_colsum on that video's operands bit for bit.  `part` holds
+ * mavlm_attention_colsum_batch_varlen_floats(R, S, H, nb) floats (the sum over all videos; 0 for bad arguments).  Checked before
+ * anything is enqueued: MAVLM_E_ARG as for mavlm_attention_colsum_batch, S[b] < 1, overlapping key ranges; MAVLM_E_SHAPE for
+ * head_dim > 128. */
+int64_t mavlm_attention_colsum_batch_varlen_floats(int32_t R, const int32_t* S, int32_t H, int32_t nb);
+int mavlm_attention_colsum_batch_varlen(const void* Q, int32_t ldq, const void* K, int32_t ldk, const int64_t* kv_off,
+                                        const float* lse2, float* part, int64_t part_floats, int32_t R, const int32_t* S,
+                                        int32_t H, int32_t nb, int32_t head_dim, float scale, int32_t dtype, void* stream);
 /* Attention maps: the mass of the normalised probabilities per (head, query group, key group),
  *   out[h][i][j] = sum over q in query group i, k in key group j of softmax(scale * Q_h K_h^T)[q][k]     fp32,
  * [H, ceil(R/q_group), ceil(S/k_group)] for groups of q_group consecutive rows and k_group consecutive keys (the last group

@@ -67,6 +67,7 @@ SIGNATURES = {
     "mavlm_step": (C.c_int, [vp, vp, i32, vp, i32, vp]),
     "mavlm_step_batch": (C.c_int, [vp, C.POINTER(vp), i32, vp, i32, vp]),
     "mavlm_step_batch_active": (C.c_int, [vp, C.POINTER(vp), i32, i32, vp, i32, vp]),
+    "mavlm_step_batch_frames": (C.c_int, [vp, C.POINTER(vp), C.POINTER(i32), i32, vp, C.c_int64, i32, vp]),
     "mavlm_video_steps": (C.c_int, [vp, i32]),
     "mavlm_batch": (C.c_int, [vp]),
     "mavlm_project_chunk": (C.c_int, [vp, vp, i32, vp]),
@@ -82,6 +83,8 @@ SIGNATURES = {
                                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
     "mavlm_fuse_emit_layout_ragged_to": (C.c_int, [vp, i32, C.POINTER(vp), vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64,
                                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
+    "mavlm_fuse_emit_layout_frames_to": (C.c_int, [vp, i32, C.POINTER(vp), vp, C.c_int64, C.POINTER(i32), vp, i32, vp, i32, vp, i32,
+                                                   i32, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
     "mavlm_fuse_emit_layout": (C.c_int, [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, C.c_int64,
                                          C.POINTER(C.c_int64), vp]),
     "mavlm_layout_rows": (C.c_int64, [C.POINTER(Config), i32, i32, i32, i32, i32, i32]),
@@ -160,6 +163,11 @@ SIGNATURES = {
     "mavlm_attention_colsum_batch_floats": (C.c_int64, [i32, i32, i32, i32]),
     "mavlm_attention_colsum_batch": (C.c_int, [vp, i32, vp, i32, C.c_int64, vp, vp, C.c_int64, i32, i32, i32, i32, i32,
                                                C.c_float, i32, vp]),
+    "mavlm_attention_batch_varlen": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, C.POINTER(i32), C.POINTER(C.c_int64),
+                                               i32, C.c_float, i32, i32, i32, vp]),
+    "mavlm_attention_colsum_batch_varlen_floats": (C.c_int64, [i32, C.POINTER(i32), i32, i32]),
+    "mavlm_attention_colsum_batch_varlen": (C.c_int, [vp, i32, vp, i32, C.POINTER(C.c_int64), vp, vp, C.c_int64, i32,
+                                                      C.POINTER(i32), i32, i32, i32, C.c_float, i32, vp]),
     "mavlm_prof_enable": (C.c_int, [i32]),
     "mavlm_prof_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), i32]),

@@ -151,7 +151,17 @@ __host__ __device__ __forceinline__ int attn3_unit_of_level(const attn3_sk_plan&
 //
 // Row batch (HB < H): the launch serves B = H / HB independent videos.  "Head" index h = b HB + hv: queries / outputs of
 // video b are the rows [b R, (b+1) R) of Q / O, its keys start kv_bs elements after video b-1's; lse2 is [B HB, R].
-template <typename T, int NW, int FR = 0>
+//
+// Variable-length row batch (VL; plain grid, 4 waves, FR = 0): video b has its own key count vl.S[b] and its keys start
+// vl.off[b] elements into K / V - the two by-value arrays replace S_all and hb * kv_bs.  Everything a segment derives from the
+// key count (its tiles, the descriptor's end, the ragged last tile, the prologue of a video with 1 - 3 tiles) is per segment
+// already, so a unit runs exactly what the plain grid of a single launch over that video's operands runs: the same bits.
+// The arrays are indexed by a wave-uniform value and stay in the kernel-argument segment (scalar loads, no private copy).
+// The instantiations without VL take an empty argument.
+template <bool VL> struct attn3_vl_arg {};
+template <> struct attn3_vl_arg<true> { int S[MAVLM_VBASE_MAX]; long long off[MAVLM_VBASE_MAX]; };
+
+template <typename T, int NW, int FR = 0, bool VL = false>
 __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* __restrict__ Q, int ldq,
                                                            const uint16_t* __restrict__ Kall, int ldk,
                                                            const uint16_t* __restrict__ Vall, int ldv,
@@ -161,7 +171,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
                                                            int HB, long long kv_bs,
                                                            float* __restrict__ fscr = nullptr,
                                                            float* __restrict__ fout = nullptr, int FP = 0, int FN = 0,
-                                                           int FNE = 0) {
+                                                           int FNE = 0, attn3_vl_arg<VL> vl = {}) {
+  static_assert(!VL || (NW == 4 && FR == 0), "the variable-length form is the plain grid of the 4-wave forward");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -226,9 +237,16 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd3_kernel(const uint16_t* _
     out_kind = tps > 0 ? 1 : 0;
   }
   const int hb = h / HB, hv = h - hb * HB;                    // video of the row batch, head inside it
-  const uint16_t* K = Kall + (size_t)hb * kv_bs + (size_t)t_lo * KT3 * ldk;
-  const uint16_t* V = Vall + (size_t)hb * kv_bs + (size_t)t_lo * KT3 * ldv;
-  const int S = (S_all - t_lo * KT3 < nt * KT3) ? S_all - t_lo * KT3 : nt * KT3;      // keys of this segment
+  int S_vid = S_all;                                          // keys of this unit's video
+  size_t kv0 = (size_t)hb * kv_bs;                            // ... and where they start (elements)
+  if constexpr (VL) {                                         // (launched on the plain grid only: t_lo = 0, one whole-unit segment)
+    S_vid = vl.S[hb];
+    kv0 = (size_t)vl.off[hb];
+    nt = (S_vid + KT3 - 1) / KT3;
+  }
+  const uint16_t* K = Kall + kv0 + (size_t)t_lo * KT3 * ldk;
+  const uint16_t* V = Vall + kv0 + (size_t)t_lo * KT3 * ldv;
+  const int S = (S_vid - t_lo * KT3 < nt * KT3) ? S_vid - t_lo * KT3 : nt * KT3;      // keys of this segment
   const int q0 = qblk * QB + wave * 32;
 
   // ---- Q fragments (B operand of S^T = K.Q^T): lane holds Q[q0+r][h*128 + 16ks + 8hh + 0..7]
@@ -1172,7 +1190,7 @@ hipError_t attn3_launch(const mavlm_attn_args& a, const attn3_launch_args& la, h
     hipLaunchKernelGGL(kern, la.grid, dim3(64 * NW), LDS, s, (const uint16_t*)a.Q, a.ldq, (const uint16_t*)a.K, a.ldk,
                        (const uint16_t*)a.V, a.ldv, (uint16_t*)a.O, a.ldo, a.lse2, a.R, a.S, a.H, la.c, la.opart, la.lpart,
                        la.tps, la.plan, la.HB, (long long)a.kv_bstride, FR ? a.frame_scr : (float*)nullptr,
-                       FR ? a.frame_out : (float*)nullptr, FR ? a.frame_keys : 0, FN, la.FNE);
+                       FR ? a.frame_out : (float*)nullptr, FR ? a.frame_keys : 0, FN, la.FNE, attn3_vl_arg<false>{});
   }
   double parts = la.ns > 1 ? (double)la.ns * a.R * a.H : 0.0;      // fp32 partial rows the merge reads
   if (la.plan.wgs > 0) {
@@ -1310,6 +1328,42 @@ static hipError_t attn3_dispatch(const mavlm_attn_args& a, int dtype, int frames
   return w8 ? attn3_launch<BF16, 8, 0>(a, la, s) : attn3_launch<BF16, 4, 0>(a, la, s);
 }
 
+// Variable-length row batch: video b attends to its own a.vl_S[b] keys, which start a.vl_off[b] elements into K / V (host
+// arrays, read here; they travel by value).  Always the plain grid - one workgroup per (video, head, 128-query block), every
+// output row has one owner, no partials, no merge: video b's rows of O / lse2 carry the bits of the plain-grid launch over that
+// video's operands alone.  Units are dispatched in the order of the equal-length row batch (blockIdx = q-block * H + head, the
+// heads of the videos side by side); the order cannot change a result.
+hipError_t mavlm_launch_attention3_varlen(const mavlm_attn_args& a, int dtype, hipStream_t s) {
+  const int nb = a.nb;
+  if (!a.vl_S || !a.vl_off || nb < 1 || nb > MAVLM_VBASE_MAX || a.H <= 0 || a.H % nb != 0 || a.R <= 0) return hipErrorInvalidValue;
+  attn3_vl_arg<true> vl = {};
+  double keys = 0.0;
+  for (int b = 0; b < nb; ++b) {
+    // 32-bit buffer offsets inside a video's key block (attn3_dispatch)
+    if (a.vl_S[b] < 1 || a.vl_off[b] < 0 || (double)a.vl_S[b] * a.ldk * 2.0 >= 2147483648.0 || (double)a.vl_S[b] * a.ldv * 2.0 >= 2147483648.0)
+      return hipErrorInvalidValue;
+    vl.S[b] = a.vl_S[b];
+    vl.off[b] = a.vl_off[b];
+    keys += a.vl_S[b];
+  }
+  const int Hv = a.H / nb;
+  const dim3 grid(((a.R + 127) / 128) * a.H);
+  const float c = a.scale * 1.44269504088896340736f;
+  const attn3_sk_plan plan = {};
+  auto launch = [&](auto kern) {
+    static mavlm_per_device_once once;
+    hipError_t e = once.dyn_lds((const void*)kern, ATTN3_LDS);
+    if (e != hipSuccess) return e;
+    mavlm_prof_scope prof(MAVLM_K_ATTN, 4.0 * a.R * keys * Hv * HD3, 2.0 * HD3 * Hv * (2.0 * a.R * nb + 2.0 * keys), s);
+    hipLaunchKernelGGL(kern, grid, dim3(256), ATTN3_LDS, s, (const uint16_t*)a.Q, a.ldq, (const uint16_t*)a.K, a.ldk,
+                       (const uint16_t*)a.V, a.ldv, (uint16_t*)a.O, a.ldo, a.lse2, a.R, 0, a.H, c, (float*)nullptr, (float*)nullptr,
+                       0, plan, Hv, 0ll, (float*)nullptr, (float*)nullptr, 0, 0, 0, vl);
+    return hipGetLastError();
+  };
+  if (dtype == MAVLM_F16) return launch(attn_fwd3_kernel<F16, 4, 0, true>);
+  return launch(attn_fwd3_kernel<BF16, 4, 0, true>);
+}
+
 hipError_t mavlm_launch_attention3_frames(const mavlm_attn_args& a, int dtype, hipStream_t s) { return attn3_dispatch(a, dtype, 1, s); }
 hipError_t mavlm_launch_attention3(const mavlm_attn_args& a, int dtype, hipStream_t s) { return attn3_dispatch(a, dtype, 0, s); }
 // the tile-entry form (FR = 2): any schedule, incl. the split-KV form of the small grids
@@ -1348,17 +1402,39 @@ constexpr int CS3_QPF = 2;                     // LDS read-ahead of the Q fragme
 // Row batch (NB): blockIdx.y is the video.  Its workgroups run the per-video schedule unchanged on that video's operands: Q, K,
 // lse2 and part are rebased here, once, so the buffer descriptors below start at the video and end at its last row - a ragged
 // last Q tile reads zeros, never the next video's rows.  The single-video instantiation takes an empty argument.
-template <bool NB> struct cs3_batch_arg {};
-template <> struct cs3_batch_arg<true> { long long kv_bstride, part_bstride; };
+//
+// Variable-length row batch (VL): video b has its own key count, and with it its own schedule - vb.S[b] keys that start
+// vb.kv_off[b] elements into K, vb.G[b] workgroups and vb.planes[b] planes (mavlm_colsum_plan of its own (R, S_b, H)), planes
+// that start vb.part_off[b] floats into `part`.  The grid is the largest G; a video's surplus workgroups leave at once.
+// The arrays are indexed by blockIdx.y (uniform) and stay in the kernel-argument segment.
+template <bool NB, bool VL = false> struct cs3_batch_arg {};
+template <> struct cs3_batch_arg<true, false> { long long kv_bstride, part_bstride; };
+template <> struct cs3_batch_arg<true, true> {
+  int S[MAVLM_VBASE_MAX], G[MAVLM_VBASE_MAX], planes[MAVLM_VBASE_MAX];
+  long long kv_off[MAVLM_VBASE_MAX], part_off[MAVLM_VBASE_MAX];
+};
 
-template <typename T, bool NB = false>
+template <typename T, bool NB = false, bool VL = false>
 __global__ __launch_bounds__(256, 4) void attn_colsum3_kernel(const uint16_t* __restrict__ Q, int ldq,
                                                               const uint16_t* __restrict__ K, int ldk,
                                                               const float* __restrict__ lse2, float* __restrict__ part,
                                                               int R, int S, int H, float c, int nkb, int nplanes,
-                                                              cs3_batch_arg<NB> vb) {
+                                                              cs3_batch_arg<NB, VL> vb) {
+  static_assert(NB || !VL, "the variable-length form is a row batch");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  if constexpr (NB) {
+  int G = (int)gridDim.x;
+  if constexpr (NB && VL) {
+    const size_t b = blockIdx.y;
+    G = vb.G[b];
+    if ((int)blockIdx.x >= G) return;                           // (whole workgroups, before any barrier)
+    S = vb.S[b];
+    nkb = (S + 127) / 128;
+    nplanes = vb.planes[b];
+    Q += b * (size_t)R * ldq;
+    K += (size_t)vb.kv_off[b];
+    lse2 += b * (size_t)H * R;
+    part += (size_t)vb.part_off[b];
+  } else if constexpr (NB) {
     const size_t b = blockIdx.y;
     Q += b * (size_t)R * ldq;
     K += b * (size_t)vb.kv_bstride;
@@ -1372,7 +1448,7 @@ __global__ __launch_bounds__(256, 4) void attn_colsum3_kernel(const uint16_t* __
   const int ntq = (R + KT3 - 1) / KT3;
   // workgroup g owns tiles [b(g), b(g+1)) of the flattened (unit, query tile) space, b(g) = g*q + min(g, rem): the first
   // `rem` workgroups take q+1 tiles, the others q  (32-bit arithmetic; the launcher checks units * tiles < 2^31)
-  const int ttot = nkb * H * ntq, G = (int)gridDim.x, gq = ttot / G, grem = ttot - gq * G;
+  const int ttot = nkb * H * ntq, gq = ttot / G, grem = ttot - gq * G;
   const int g = (int)blockIdx.x;
   int b0 = g * gq + (g < grem ? g : grem);
   const int b1 = b0 + gq + (g < grem ? 1 : 0);
@@ -1581,6 +1657,19 @@ __global__ void colsum_planes_reduce_kernel(float* __restrict__ part, size_t n, 
   for (int p = 1; p < nplanes; ++p) v += part[(size_t)p * n + i];
   part[i] = v;
 }
+// the same for a variable-length row batch: video blockIdx.y has H * S_b sums in planes_b planes at its own offset (the grid
+// covers the longest video)
+__global__ void colsum_planes_reduce_vl_kernel(float* __restrict__ part, int H, cs3_batch_arg<true, true> vb) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = blockIdx.y;
+  const size_t n = (size_t)H * vb.S[b];
+  if (i >= n) return;
+  const int nplanes = vb.planes[b];
+  part += (size_t)vb.part_off[b];
+  float v = part[i];
+  for (int p = 1; p < nplanes; ++p) v += part[(size_t)p * n + i];
+  part[i] = v;
+}
 
 }  // namespace
 
@@ -1634,7 +1723,7 @@ hipError_t mavlm_launch_colsum3(const mavlm_colsum_args& a, int dtype, hipStream
   {
     mavlm_prof_scope prof(MAVLM_K_COLSUM, 2.0 * nb * a.R * (double)a.S * a.H * HD3, 2.0 * nb * HD3 * a.H * ((double)a.R + a.S), s);
     if (nb > 1) {
-      const cs3_batch_arg<true> vb = {a.kv_bstride, a.part_bstride};
+      const cs3_batch_arg<true, false> vb = {a.kv_bstride, a.part_bstride};
       if (dtype == MAVLM_F16)
         hipLaunchKernelGGL((attn_colsum3_kernel<F16, true>), dim3(G, nb), dim3(256), CS3_LDS, s, (const uint16_t*)a.Q, a.ldq,
                            (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, nkb, planes, vb);
@@ -1643,10 +1732,10 @@ hipError_t mavlm_launch_colsum3(const mavlm_colsum_args& a, int dtype, hipStream
                            (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, nkb, planes, vb);
     } else if (dtype == MAVLM_F16) {
       hipLaunchKernelGGL((attn_colsum3_kernel<F16, false>), dim3(G), dim3(256), CS3_LDS, s, (const uint16_t*)a.Q, a.ldq,
-                         (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, nkb, planes, cs3_batch_arg<false>{});
+                         (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, nkb, planes, cs3_batch_arg<false, false>{});
     } else {
       hipLaunchKernelGGL((attn_colsum3_kernel<BF16, false>), dim3(G), dim3(256), CS3_LDS, s, (const uint16_t*)a.Q, a.ldq,
-                         (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, nkb, planes, cs3_batch_arg<false>{});
+                         (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, a.S, a.H, c, nkb, planes, cs3_batch_arg<false, false>{});
     }
   }
   if (!a.keep_planes && planes > 1) {
@@ -1654,6 +1743,51 @@ hipError_t mavlm_launch_colsum3(const mavlm_colsum_args& a, int dtype, hipStream
     mavlm_prof_scope prof(MAVLM_K_MISC, 0.0, 4.0 * nb * (planes + 1) * (double)n, s);
     hipLaunchKernelGGL(colsum_planes_reduce_kernel, dim3((unsigned)((n + 255) / 256), nb), dim3(256), 0, s, a.part, n, planes,
                        (size_t)(nb > 1 ? a.part_bstride : 0));
+  }
+  return hipGetLastError();
+}
+
+// Variable-length row batch of the column sums (a.vl_S / a.vl_kv_off: host arrays of a.nb entries, read here).  Video b runs
+// the balanced schedule of its own (R, S_b, H) - the one mavlm_launch_colsum3 gives it alone - and writes its planes
+// sum_{v<b} mavlm_colsum_part_floats(R, S_v, H) floats into a.part: the bits of nb single launches.
+hipError_t mavlm_launch_colsum3_varlen(const mavlm_colsum_args& a, int dtype, hipStream_t s) {
+  const int nb = a.nb;
+  if (!a.vl_S || !a.vl_kv_off || nb < 1 || nb > MAVLM_VBASE_MAX || a.R <= 0 || a.H <= 0) return hipErrorInvalidValue;
+  if ((double)a.R * a.ldq * 2.0 >= 2147483648.0) return hipErrorInvalidValue;      // 32-bit buffer offsets
+  cs3_batch_arg<true, true> vb = {};
+  int Gmax = 0, pmax = 1, Smax = 0;
+  long long off = 0;
+  double keys = 0.0;
+  for (int b = 0; b < nb; ++b) {
+    const int S = a.vl_S[b];
+    if (S < 1 || a.vl_kv_off[b] < 0) return hipErrorInvalidValue;
+    if ((double)((S + 127) / 128) * a.H * ((a.R + KT3 - 1) / KT3) >= 2.0e9) return hipErrorInvalidValue;   // 32-bit schedule arithmetic
+    int planes = 1;
+    vb.S[b] = S;
+    vb.G[b] = mavlm_colsum_plan(a.R, S, a.H, &planes);
+    vb.planes[b] = planes;
+    vb.kv_off[b] = a.vl_kv_off[b];
+    vb.part_off[b] = off;
+    off += (long long)mavlm_colsum_part_floats(a.R, S, a.H);
+    Gmax = vb.G[b] > Gmax ? vb.G[b] : Gmax;
+    pmax = planes > pmax ? planes : pmax;
+    Smax = S > Smax ? S : Smax;
+    keys += S;
+  }
+  const float c = a.scale * 1.44269504088896340736f;
+  {
+    mavlm_prof_scope prof(MAVLM_K_COLSUM, 2.0 * a.R * keys * a.H * HD3, 2.0 * HD3 * a.H * ((double)a.R * nb + keys), s);
+    if (dtype == MAVLM_F16)
+      hipLaunchKernelGGL((attn_colsum3_kernel<F16, true, true>), dim3(Gmax, nb), dim3(256), CS3_LDS, s, (const uint16_t*)a.Q, a.ldq,
+                         (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, 0, a.H, c, 0, 0, vb);
+    else
+      hipLaunchKernelGGL((attn_colsum3_kernel<BF16, true, true>), dim3(Gmax, nb), dim3(256), CS3_LDS, s, (const uint16_t*)a.Q, a.ldq,
+                         (const uint16_t*)a.K, a.ldk, a.lse2, a.part, a.R, 0, a.H, c, 0, 0, vb);
+  }
+  if (!a.keep_planes && pmax > 1) {
+    const size_t n = (size_t)a.H * Smax;
+    mavlm_prof_scope prof(MAVLM_K_MISC, 0.0, 4.0 * (pmax + 1) * (double)a.H * keys, s);
+    hipLaunchKernelGGL(colsum_planes_reduce_vl_kernel, dim3((unsigned)((n + 255) / 256), nb), dim3(256), 0, s, a.part, a.H, vb);
   }
   return hipGetLastError();
 }

@@ -64,6 +64,7 @@ struct mavlm_ctx {
   int nb = 1;                     // videos of the step / emit launch in flight (B outside mavlm_step_batch_active)
   size_t fscr_floats = 0, fout_floats = 0;
   size_t o_xsplit = 0, o_xgsplit = 0, o_xfscr = 0, o_xfout = 0;
+  size_t o_vlpart = 0, vlpart_floats = 0;   // column-sum planes of a step with per-video frame counts (mavlm_step_batch_frames)
   int n_active = 0;               // videos of the last step since mavlm_reset (0 = none yet)
   int vsteps[MAVLM_MAX_BATCH] = {};   // steps of each video since mavlm_reset
 };
@@ -328,6 +329,22 @@ void carve(mavlm_ctx* x) {
   if (mx.fscr_floats > x->fscr_floats) { x->o_xfscr = o; o += al(mx.fscr_floats * 4); }
   if (mx.fout_floats > x->fout_floats) { x->o_xfout = o; o += al(mx.fout_floats * 4); }
   // (the exchange scratch of the fused Residual kernel grows with the rows: the own region covers every smaller count)
+  // Steps whose videos bring different frame counts (mavlm_step_batch_frames): the column-sum planes of ALL videos of one launch,
+  // video after video (o_part holds one video's).  Behind every other region; heads of <= 128 columns only (the wide heads run
+  // their column sums video by video through o_part).
+  x->o_vlpart = x->vlpart_floats = 0;
+  if (!wide_heads(x->cfg)) {
+    const mavlm_config& c = x->cfg;
+    const int R1 = q_tokens(c) * c.patches;
+    size_t fl = 0;
+    for (int f = 1; f <= c.max_chunk_frames; ++f) {
+      const size_t v = mavlm_colsum_part_floats(R1, f * c.patches, c.heads);
+      if (v > fl) fl = v;
+    }
+    x->vlpart_floats = fl * (size_t)(B < MAVLM_VBASE_MAX ? B : MAVLM_VBASE_MAX);
+    x->o_vlpart = o;
+    o += al(x->vlpart_floats * 4);
+  }
   x->total = o;
 }
 
@@ -423,7 +440,10 @@ int dense_ln(mavlm_ctx* x, hipStream_t s, const void* A, int lda, const void* W,
 // frame_rows (out): rows of the partial frame sums per video when `frames` (argument of the finish kernel)
 int attn_block(mavlm_ctx* x, hipStream_t s, const mavlm_attn_weights& aw, const void* xq, const void* K, int ldk,
                const void* V, int ldv, long long kv_bs, int S, void* out, float* lse2, int frames = 0,
-               int* frame_rows = nullptr, const void* q_pre = nullptr) {
+               int* frame_rows = nullptr, const void* q_pre = nullptr, const int* vl_S = nullptr,
+               const long long* vl_off = nullptr) {
+  // vl_S / vl_off (a step whose videos bring different frame counts; never with `frames`): video b has vl_S[b] keys that start
+  // vl_off[b] elements into K / V - S and kv_bs are not read
   const mavlm_config& c = x->cfg;
   // (B: the videos of this step - all of the context's, or the active prefix; Bc > 1: the row-batch rules)
   const int B = x->nb, Bc = nbatch(c), R1 = q_tokens(c) * c.patches, R = R1 * B, D = c.hidden, H = c.heads, dt = c.dtype,
@@ -434,7 +454,23 @@ int attn_block(mavlm_ctx* x, hipStream_t s, const mavlm_attn_weights& aw, const 
   mavlm_attn_args a;
   a.Q = x->q_used; a.ldq = Dp; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = ws(x, x->o_ctx); a.ldo = Dp;
   a.lse2 = lse2; a.R = R1; a.S = S; a.H = H * B; a.nb = B; a.kv_bstride = kv_bs; a.scale = attn_scale(c);
-  if (wide_heads(c)) {
+  if (vl_S && wide_heads(c)) {
+    // head_dim 448 has no variable-length kernel: one launch of the forward per video, plain grid (the stacked GEMMs around it
+    // are where a row batch gains at this width)
+    for (int b = 0; b < B; ++b) {
+      mavlm_attn_args a1 = a;
+      a1.Q = (const char*)a.Q + (size_t)b * R1 * Dp * 2;
+      a1.O = (char*)a.O + (size_t)b * R1 * Dp * 2;
+      a1.K = (const char*)K + (size_t)vl_off[b] * 2;
+      a1.V = (const char*)V + (size_t)vl_off[b] * 2;
+      a1.lse2 = lse2 ? lse2 + (size_t)b * H * R1 : nullptr;
+      a1.S = vl_S[b]; a1.H = H; a1.nb = 1; a1.kv_bstride = 0; a1.split_ws = nullptr;
+      MAVLM_TRY(mavlm_launch_attention_hd(a1, c.hidden / c.heads, dt, s));
+    }
+  } else if (vl_S) {
+    a.vl_S = vl_S; a.vl_off = vl_off;
+    MAVLM_TRY(mavlm_launch_attention3_varlen(a, dt, s));
+  } else if (wide_heads(c)) {
     // wide heads (448: the OneVision-7B width): the row batch is the grid's z dimension, or - when its units exceed the 256
     // workgroups of one-per-CU - the levelled stream-K plan over the (video, head) pairs; a single video with a small grid takes
     // the kernel's split-KV form.  The schedule is part of the result: the plan is taken only when the carved workspace covers
@@ -525,7 +561,12 @@ int step_maps(mavlm_ctx* x, hipStream_t s, const char* K, int ldk, long long kv_
   return 0;
 }
 
-int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scores, int32_t scores_f32, hipStream_t s) {
+// Fv (mavlm_step_batch_frames; null = every video brings F frames): video b's chunk is [Fv[b], P, D].  The chunk K/V of the videos
+// then lie back to back in the chunk K/V buffer (prefix offsets), every formation layer runs the variable-length forward, and the
+// frame scores of the last layer come from the variable-length column-sum launch (never fused into the forward: the memory is
+// the same bits with and without scores, under every frame-score mode); video b's Fv[b] scores land at frame_scores + b * ld_scores.
+int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scores, int32_t scores_f32, hipStream_t s,
+              const int32_t* Fv = nullptr, long long ld_scores = 0) {
   const mavlm_config& c = x->cfg;
   // R1: memory rows of one video (keys of the evolution, ring strides); Rq1: the rows of them this context computes (row
   // shard: q_tokens memory tokens from row r0 on; else all); R: rows of the row-wise operators
@@ -578,6 +619,17 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
   // ---- memory formation (MemoryController.py:132-133): K/V of the chunk for all L layers in one GEMM per video (the shape
   // does not depend on the memory rows: nothing to gain from stacking, and the videos' frames stay where they are)
   const int ldkv = 2 * L * Dp;
+  int vl_S[MAVLM_VBASE_MAX];
+  long long vl_off[MAVLM_VBASE_MAX];         // elements into the chunk K/V buffer
+  if (Fv) {
+    if (B > MAVLM_VBASE_MAX || x->maps) return MAVLM_E_STATE;
+    long long o = 0;
+    for (int b = 0; b < B; ++b) {
+      vl_S[b] = Fv[b] * c.patches;
+      vl_off[b] = o;
+      o += (long long)vl_S[b] * ldkv;
+    }
+  }
   // Which chunk K/V buffer this step reads: the one a projection made ahead for exactly this step and chunk sits in (the step
   // then waits for it, nothing else); otherwise buffer 0 - or buffer 1 while a projection for a LATER step owns buffer 0.  A
   // projection made for this step but another chunk is discarded (its buffer is waited for before anything overwrites it).
@@ -604,15 +656,15 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
   x->pre_hits += pre ? 1 : 0;       // a projection made ahead for exactly this chunk
   char* kvs = ws(x, rb ? x->o_kv2 : x->o_kv);
   for (int b = 0; b < B && !pre; ++b)
-    MAVLM_TRY(gemm_x(x, s, segs[b], D, x->w.w_kv_seg, D, x->w.b_kv_seg, kvs + (size_t)b * S * ldkv * 2, ldkv, S, ldkv, D,
-                     MAVLM_EPI_BIAS));
+    MAVLM_TRY(gemm_x(x, s, segs[b], D, x->w.w_kv_seg, D, x->w.b_kv_seg, kvs + (Fv ? (size_t)vl_off[b] : (size_t)b * S * ldkv) * 2, ldkv,
+                     Fv ? vl_S[b] : S, ldkv, D, MAVLM_EPI_BIAS));
   for (int l = 0; l < L; ++l) {
     const bool last = l == L - 1;
     const bool want_scores = last && frame_scores != nullptr;
     const char* Kl = kvs + (size_t)(2 * l) * Dp * 2;
     const char* Vl = Kl + (size_t)Dp * 2;
     // frame scores: fused into this layer's forward (default), or the column-sum pass over its Q / K / lse2
-    const int fused_scores = want_scores ? step_frames_fused(x, S) : 0;
+    const int fused_scores = want_scores && !Fv ? step_frames_fused(x, S) : 0;
     float* lse = want_scores ? (float*)ws(x, x->o_lse) : maps_lse;     // (the fused form does not need it; kept for inspection)
     int frows = 0;
     // First step, first layer: cur is the packed initial memory and Q = mem0 . Wq^T + bq depends on the bound weights alone -
@@ -638,7 +690,7 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
       if (hit) q_pre = ws(x, x->o_q0);
     }
     int rc = attn_block(x, s, x->w.layer_attn[l], cur, Kl, ldkv, Vl, ldkv, (long long)S * ldkv, S, ws(x, x->o_a), lse,
-                        fused_scores, &frows, q_pre);
+                        fused_scores, &frows, q_pre, Fv ? vl_S : nullptr, Fv ? vl_off : nullptr);
     if (rc) return rc;
     if (x->maps) {        // [H, M, F] of layer l: query group = one memory token, key group = one frame
       rc = step_maps(x, s, Kl, ldkv, (long long)S * ldkv, S, c.patches, 0, (size_t)l * H * q_tokens(c) * F);
@@ -646,6 +698,35 @@ int step_impl(mavlm_ctx* x, const void* const* segs, int32_t F, void* frame_scor
     }
     if (fused_scores) {
       MAVLM_TRY(mavlm_launch_frame_finish(p_fout(x), frows, B, F, c.patches, frame_scores, scores_f32, dt, s));
+    } else if (want_scores && Fv && !wide_heads(c)) {
+      // one column-sum launch for all videos, each on the schedule of its own key count, its planes at its prefix offset; the
+      // finishing kernel adds a video's planes in order (as behind a single video's pass)
+      mavlm_colsum_args ca;
+      ca.Q = x->q_used; ca.ldq = Dp; ca.K = Kl; ca.ldk = ldkv; ca.lse2 = lse; ca.part = (float*)ws(x, x->o_vlpart);
+      ca.R = Rq1; ca.S = 0; ca.H = H; ca.scale = attn_scale(c); ca.nb = B; ca.keep_planes = 1;
+      ca.vl_S = vl_S; ca.vl_kv_off = vl_off;
+      size_t need = 0;
+      for (int b = 0; b < B; ++b) need += mavlm_colsum_part_floats(Rq1, vl_S[b], H);
+      if (!x->o_vlpart || need > x->vlpart_floats) return MAVLM_E_STATE;
+      MAVLM_TRY(mavlm_launch_colsum3_varlen(ca, dt, s));
+      size_t po = 0;
+      for (int b = 0; b < B; ++b) {
+        int planes = 1;
+        mavlm_colsum_plan(Rq1, vl_S[b], H, &planes);
+        void* fs = scores_f32 ? (void*)((float*)frame_scores + (size_t)b * ld_scores) : (void*)((uint16_t*)frame_scores + (size_t)b * ld_scores);
+        MAVLM_TRY(mavlm_launch_frame_scores(ca.part + po, planes, H, vl_S[b], Fv[b], c.patches, fs, scores_f32, dt, s));
+        po += mavlm_colsum_part_floats(Rq1, vl_S[b], H);
+      }
+    } else if (want_scores && Fv) {
+      for (int b = 0; b < B; ++b) {          // (wide heads: the per-video pass, on each video's own key count)
+        mavlm_colsum_args ca;
+        ca.Q = (const char*)x->q_used + (size_t)b * Rq1 * Dp * 2; ca.ldq = Dp; ca.K = Kl + (size_t)vl_off[b] * 2; ca.ldk = ldkv;
+        ca.lse2 = lse + (size_t)b * H * Rq1; ca.part = (float*)ws(x, x->o_part);
+        ca.R = Rq1; ca.S = vl_S[b]; ca.H = H; ca.scale = attn_scale(c);
+        MAVLM_TRY(mavlm_launch_colsum_hd(ca, c.hidden / c.heads, dt, s));
+        void* fs = scores_f32 ? (void*)((float*)frame_scores + (size_t)b * ld_scores) : (void*)((uint16_t*)frame_scores + (size_t)b * ld_scores);
+        MAVLM_TRY(mavlm_launch_frame_scores(ca.part, 1, H, vl_S[b], Fv[b], c.patches, fs, scores_f32, dt, s));
+      }
     } else if (want_scores) {
       for (int b = 0; b < B; ++b) {          // (one pass per video: the column-sum kernels know nothing of the row batch)
         mavlm_colsum_args ca;
@@ -964,6 +1045,34 @@ int mavlm_step_batch_active(mavlm_ctx* x, const void* const* segs, int32_t n_act
   return rc;
 }
 
+int mavlm_step_batch_frames(mavlm_ctx* x, const void* const* segs, const int32_t* F, int32_t n_active, void* frame_scores,
+                            int64_t ld_scores, int32_t scores_f32, void* stream) {
+  // every check comes before anything is enqueued
+  if (!x || !segs || !F) return MAVLM_E_ARG;
+  if (n_active < 1 || n_active > nbatch(x->cfg)) return MAVLM_E_ARG;
+  if (nbatch(x->cfg) < 2) return MAVLM_E_STATE;            // (a single video steps through mavlm_step)
+  bool equal = true;
+  int fmax = 0;
+  for (int b = 0; b < n_active; ++b) {
+    if (!segs[b]) return MAVLM_E_ARG;
+    if (F[b] < 1 || F[b] > x->cfg.max_chunk_frames) return MAVLM_E_ARG;
+    equal = equal && F[b] == F[0];
+    fmax = F[b] > fmax ? F[b] : fmax;
+  }
+  if (frame_scores && ld_scores < fmax) return MAVLM_E_ARG;
+  if (!x->has_w || !x->has_b) return MAVLM_E_STATE;
+  if (x->n_active != 0 && n_active > x->n_active) return MAVLM_E_STATE;            // the prefix only shrinks
+  // all videos with the same frame count and scores packed [n_active, F]: the existing step, bit for bit
+  if (equal && (!frame_scores || ld_scores == F[0]))
+    return mavlm_step_batch_active(x, segs, n_active, F[0], frame_scores, scores_f32, stream);
+  if (n_active > MAVLM_VBASE_MAX) return MAVLM_E_ARG;       // the per-video counts travel by value
+  if (x->maps) return MAVLM_E_STATE;                       // attention maps of videos with different frame counts: not provided
+  x->nb = n_active;
+  const int rc = step_impl(x, segs, fmax, frame_scores, scores_f32, (hipStream_t)stream, F, ld_scores);
+  x->nb = nbatch(x->cfg);
+  return rc;
+}
+
 int mavlm_video_steps(const mavlm_ctx* x, int32_t b) {
   if (!x || b < 0 || b >= nbatch(x->cfg)) return MAVLM_E_ARG;
   return x->vsteps[b];
@@ -1173,13 +1282,25 @@ int mavlm_fuse_emit_layout_batch_to(mavlm_ctx* x, const void* const* x_pe, const
 namespace {
 // mavlm_fuse_emit_layout_ragged_to.  Videos 0 .. nv-1 in the context's longest-first order: vsteps is non-increasing, so the
 // videos that hold a ring slot, and the videos with one block length, are ranges that start at video 0 / are contiguous.
+// n_fine_v (mavlm_fuse_emit_layout_frames_to; null = every video has n_fine fine frames and fine_ld = n_fine): video b has
+// n_fine_v[b] fine frames, its index row starts b * fine_ld entries into fine_idx.  The literal rows and the fine frames then
+// run per range of consecutive videos with one (memories, fine frames) pair - with a constant count the same launches as before.
 int ragged_emit_impl(mavlm_ctx* x, int nv, const void* const* x_pe, const int64_t* fine_idx, int32_t n_fine, const void* mem_prompt,
                      int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt, const void* newline,
                      int32_t with_frames, int32_t layout, void* out, int64_t out_rows, const int64_t* dst_row, int64_t* rows,
-                     hipStream_t s) {
+                     hipStream_t s, const int32_t* n_fine_v = nullptr, int64_t fine_ld = 0) {
   const mavlm_config& c = x->cfg;
   const int Bc = nbatch(c), R1 = c.mem_tokens * c.patches, D = c.hidden, I = c.inter, dt = c.dtype, cap = c.cache_cap;
   if (nv < 1 || nv > Bc || nv > MAVLM_VBASE_MAX) return MAVLM_E_ARG;
+  int nf[MAVLM_VBASE_MAX];
+  for (int b = 0; b < nv; ++b) {
+    nf[b] = n_fine_v ? n_fine_v[b] : n_fine;
+    if (nf[b] < 0 || (n_fine_v && nf[b] > fine_ld)) return MAVLM_E_ARG;
+    if (nf[b] > n_fine) n_fine = nf[b];                          // (from here on: the largest count)
+  }
+  if (!n_fine_v) fine_ld = n_fine;
+  // (the fuser's second GEMM writes through the row map of the 256-column-tile kernels: the new export says so up front)
+  if (n_fine_v && D % 256 != 0) return MAVLM_E_SHAPE;
   if (n_mem_prompt < 0 || n_frame_prompt < 0 || n_fine < 0 || (n_mem_prompt && !mem_prompt) ||
       (with_frames && ((n_frame_prompt && !frame_prompt) || (n_fine && (!x_pe || !fine_idx)))))
     return MAVLM_E_ARG;
@@ -1190,13 +1311,13 @@ int ragged_emit_impl(mavlm_ctx* x, int nv, const void* const* x_pe, const int64_
     return MAVLM_E_ARG;
   // per video: memories, place of the first fine-frame row, block length; then the destinations - on the host, before the first launch
   int nm[MAVLM_VBASE_MAX];
-  int64_t need[MAVLM_VBASE_MAX], r_fine[MAVLM_VBASE_MAX];
-  const int64_t fine_rows = block_rows((int64_t)n_fine * c.patches, layout, gap);
+  int64_t need[MAVLM_VBASE_MAX], r_fine[MAVLM_VBASE_MAX], fine_rows[MAVLM_VBASE_MAX];
   for (int b = 0; b < nv; ++b) {
     nm[b] = x->vsteps[b] < cap ? x->vsteps[b] : cap;
+    fine_rows[b] = block_rows((int64_t)nf[b] * c.patches, layout, gap);
     const int64_t r_fp = n_mem_prompt + block_rows((int64_t)nm[b] * R1, layout, gap);
     r_fine[b] = r_fp + n_frame_prompt;
-    need[b] = with_frames ? r_fine[b] + fine_rows : r_fp;
+    need[b] = with_frames ? r_fine[b] + fine_rows[b] : r_fp;
   }
   for (int b = 0; b < nv; ++b) {
     if (dst_row[b] < 0 || dst_row[b] > out_rows - need[b]) return MAVLM_E_ARG;
@@ -1207,7 +1328,7 @@ int ragged_emit_impl(mavlm_ctx* x, int nv, const void* const* x_pe, const int64_
   if (!x->w.w_f1 || !x->w.b_f1 || !x->w.w_f2 || !x->w.b_f2_type0 || (with_frames && !x->w.type1)) return MAVLM_E_STATE;
   for (int b = 0; b < nv; ++b) {
     if (nm[b] == 0 || (b > 0 && x->vsteps[b] > x->vsteps[b - 1])) return MAVLM_E_STATE;
-    if (with_frames && n_fine && !x_pe[b]) return MAVLM_E_ARG;
+    if (with_frames && nf[b] && !x_pe[b]) return MAVLM_E_ARG;
   }
   const size_t rowb = (size_t)D * 2;
   // ---- the literal rows: one launch per range of videos with the same number of memories (the rows of copy_rows_kernel's runs
@@ -1216,12 +1337,12 @@ int ragged_emit_impl(mavlm_ctx* x, int nv, const void* const* x_pe, const int64_
   for (int b = 0; b < nv; ++b) base[b] = (long long)dst_row[b] * D;
   for (int b0 = 0; b0 < nv;) {
     int b1 = b0 + 1;
-    while (b1 < nv && nm[b1] == nm[b0]) ++b1;
+    while (b1 < nv && nm[b1] == nm[b0] && nf[b1] == nf[b0]) ++b1;
     const int64_t feat = (int64_t)nm[b0] * R1, mem_rows = block_rows(feat, layout, gap), r_fp = n_mem_prompt + mem_rows;
-    const int nl_mem = (int)(mem_rows - feat), nl_fine = (int)(fine_rows - (int64_t)n_fine * c.patches);
+    const int nl_mem = (int)(mem_rows - feat), nl_fine = (int)(fine_rows[b0] - (int64_t)nf[b0] * c.patches);
     const void* src[4] = {mem_prompt, newline, frame_prompt, newline};
     const int cnt[4] = {n_mem_prompt, nl_mem, with_frames ? n_frame_prompt : 0, with_frames ? nl_fine : 0};
-    const long long dst[4] = {0, n_mem_prompt + (gap > 0 ? gap : feat), r_fp, r_fine[b0] + (gap > 0 ? gap : (int64_t)n_fine * c.patches)};
+    const long long dst[4] = {0, n_mem_prompt + (gap > 0 ? gap : feat), r_fp, r_fine[b0] + (gap > 0 ? gap : (int64_t)nf[b0] * c.patches)};
     const int rep[4] = {0, gap > 0 ? gap + 1 : 0, 0, gap > 0 ? gap + 1 : 0};
     MAVLM_TRY(mavlm_launch_copy_rows(src, cnt, dst, 4, out, 0, b1 - b0, D, s, rep, base + b0));
     b0 = b1;
@@ -1262,7 +1383,13 @@ int ragged_emit_impl(mavlm_ctx* x, int nv, const void* const* x_pe, const int64_
   if (with_frames && n_fine) {
     long long fb[MAVLM_VBASE_MAX];
     for (int b = 0; b < nv; ++b) fb[b] = base[b] + (long long)r_fine[b] * D;
-    MAVLM_TRY(mavlm_launch_row_add_batch(x_pe, fine_idx, x->w.type1, out, 0, nv, n_fine, c.patches, D, dt, s, gap, fb, n_fine));
+    for (int b0 = 0; b0 < nv;) {            // (one launch per range of videos with one fine-frame count: all of them, when it is constant)
+      int b1 = b0 + 1;
+      while (b1 < nv && nf[b1] == nf[b0]) ++b1;
+      MAVLM_TRY(mavlm_launch_row_add_batch(x_pe + b0, fine_idx + (size_t)b0 * fine_ld, x->w.type1, out, 0, b1 - b0, nf[b0], c.patches, D,
+                                           dt, s, gap, fb + b0, fine_ld));
+      b0 = b1;
+    }
   }
   for (int b = 0; b < nv; ++b) rows[b] = need[b];
   return 0;
@@ -1277,6 +1404,17 @@ int mavlm_fuse_emit_layout_ragged_to(mavlm_ctx* x, int32_t n_videos, const void*
   if (nbatch(x->cfg) < 2) return MAVLM_E_STATE;
   return ragged_emit_impl(x, n_videos, x_pe, fine_idx, n_fine, mem_prompt, n_mem_prompt, frame_prompt, n_frame_prompt, newline,
                           with_frames, layout, out, out_rows, dst_row, rows, (hipStream_t)stream);
+}
+
+int mavlm_fuse_emit_layout_frames_to(mavlm_ctx* x, int32_t n_videos, const void* const* x_pe, const int64_t* fine_idx,
+                                     int64_t fine_ld, const int32_t* n_fine, const void* mem_prompt, int32_t n_mem_prompt,
+                                     const void* frame_prompt, int32_t n_frame_prompt, const void* newline, int32_t with_frames,
+                                     int32_t layout, void* out, int64_t out_rows, const int64_t* dst_row, int64_t* rows,
+                                     void* stream) {
+  if (!x || !out || !rows || !dst_row || !n_fine || out_rows < 0 || fine_ld < 0) return MAVLM_E_ARG;
+  if (nbatch(x->cfg) < 2) return MAVLM_E_STATE;
+  return ragged_emit_impl(x, n_videos, x_pe, fine_idx, 0, mem_prompt, n_mem_prompt, frame_prompt, n_frame_prompt, newline,
+                          with_frames, layout, out, out_rows, dst_row, rows, (hipStream_t)stream, n_fine, fine_ld);
 }
 
 int mavlm_fuse_emit(mavlm_ctx* x, const void* x_pe, const int64_t* fine_idx, int32_t n_fine, const void* mem_prompt,
@@ -1473,6 +1611,37 @@ int mavlm_attention_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk
   return e == hipErrorInvalidValue ? MAVLM_E_ARG : (int)e;
 }
 
+// per-video key ranges of a variable-length row batch: counts, alignment, pairwise disjoint [off, off + S * ld)
+static int varlen_ranges_bad(const int32_t* S, const int64_t* off, int32_t nb, int64_t ld) {
+  if (!S || !off || nb < 1 || nb > MAVLM_VBASE_MAX) return 1;
+  for (int b = 0; b < nb; ++b) {
+    if (S[b] < 1 || off[b] < 0 || (off[b] & 7)) return 1;
+    for (int a = 0; a < b; ++a)
+      if (off[a] < off[b] + (int64_t)S[b] * ld && off[b] < off[a] + (int64_t)S[a] * ld) return 1;
+  }
+  return 0;
+}
+
+int mavlm_attention_batch_varlen(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, void* O,
+                                 int32_t ldo, float* lse2, int32_t R, const int32_t* S, const int64_t* kv_off, int32_t H,
+                                 float scale, int32_t nb, int32_t head_dim, int32_t dtype, void* stream) {
+  // every check comes before the launch
+  if (!Q || !K || !V || !O || R <= 0 || nb < 1 || nb > MAVLM_VBASE_MAX || H <= 0 || H % nb != 0 || (dtype != 0 && dtype != 1))
+    return MAVLM_E_ARG;
+  if (head_dim <= 0 || head_dim > 128) return MAVLM_E_SHAPE;
+  const int Hv = H / nb;
+  if ((ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 3) || ldq < Hv * 128 || ldk < Hv * 128 || ldv < Hv * 128 || ldo < Hv * 128)
+    return MAVLM_E_ARG;
+  if (varlen_ranges_bad(S, kv_off, nb, ldk) || varlen_ranges_bad(S, kv_off, nb, ldv)) return MAVLM_E_ARG;
+  long long off[MAVLM_VBASE_MAX];
+  for (int b = 0; b < nb; ++b) off[b] = kv_off[b];
+  mavlm_attn_args a;
+  a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = O; a.ldo = ldo; a.lse2 = lse2;
+  a.R = R; a.S = 0; a.H = H; a.scale = scale; a.nb = nb; a.vl_S = S; a.vl_off = off;
+  hipError_t e = mavlm_launch_attention3_varlen(a, dtype, (hipStream_t)stream);
+  return e == hipErrorInvalidValue ? MAVLM_E_ARG : (int)e;
+}
+
 int mavlm_attention_colsum_hd(const void* Q, int32_t ldq, const void* K, int32_t ldk, const float* lse2, float* part,
                               int32_t R, int32_t S, int32_t H, int32_t head_dim, float scale, int32_t dtype, void* stream) {
   if (!Q || !K || !lse2 || !part || R <= 0 || S <= 0 || H <= 0 || (ldq & 7) || (ldk & 7)) return MAVLM_E_ARG;
@@ -1538,6 +1707,39 @@ int mavlm_attention_colsum_batch(const void* Q, int32_t ldq, const void* K, int3
       e = mavlm_launch_colsum(a, dtype, (hipStream_t)stream);
     }
   }
+  return e == hipErrorInvalidValue ? MAVLM_E_ARG : (int)e;
+}
+
+// ---- the same with per-video key counts (head columns of 128): every video on the schedule of its own shape
+int64_t mavlm_attention_colsum_batch_varlen_floats(int32_t R, const int32_t* S, int32_t H, int32_t nb) {
+  if (R <= 0 || H <= 0 || !S || nb < 1 || nb > MAVLM_VBASE_MAX) return 0;
+  int64_t n = 0;
+  for (int b = 0; b < nb; ++b) {
+    if (S[b] < 1) return 0;
+    n += (int64_t)mavlm_colsum_part_floats(R, S[b], H);
+  }
+  return n;
+}
+
+int mavlm_attention_colsum_batch_varlen(const void* Q, int32_t ldq, const void* K, int32_t ldk, const int64_t* kv_off,
+                                        const float* lse2, float* part, int64_t part_floats, int32_t R, const int32_t* S,
+                                        int32_t H, int32_t nb, int32_t head_dim, float scale, int32_t dtype, void* stream) {
+  // every check comes before any launch
+  if (!Q || !K || !lse2 || !part || R <= 0 || H <= 0 || nb < 1 || nb > MAVLM_VBASE_MAX || (dtype != 0 && dtype != 1)) return MAVLM_E_ARG;
+  if (head_dim <= 0 || head_dim > 128) return MAVLM_E_SHAPE;
+  if ((ldq & 7) || (ldk & 7) || ldq < H * 128 || ldk < H * 128) return MAVLM_E_ARG;
+  if (varlen_ranges_bad(S, kv_off, nb, ldk)) return MAVLM_E_ARG;
+  const int64_t need = mavlm_attention_colsum_batch_varlen_floats(R, S, H, nb);
+  if (need <= 0 || part_floats < need) return MAVLM_E_ARG;
+  if ((double)R * ldq * 2.0 >= 2147483648.0) return MAVLM_E_ARG;            // the 32-bit offsets of the pipelined kernel
+  for (int b = 0; b < nb; ++b)
+    if ((double)((S[b] + 127) / 128) * H * ((R + 63) / 64) >= 2.0e9) return MAVLM_E_ARG;     // ... and its schedule arithmetic
+  long long off[MAVLM_VBASE_MAX];
+  for (int b = 0; b < nb; ++b) off[b] = kv_off[b];
+  mavlm_colsum_args a;
+  a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.lse2 = lse2; a.part = part; a.R = R; a.S = 0; a.H = H; a.scale = scale;
+  a.nb = nb; a.vl_S = S; a.vl_kv_off = off;
+  hipError_t e = mavlm_launch_colsum3_varlen(a, dtype, (hipStream_t)stream);
   return e == hipErrorInvalidValue ? MAVLM_E_ARG : (int)e;
 }
 

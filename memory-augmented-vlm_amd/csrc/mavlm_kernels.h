@@ -107,8 +107,14 @@ struct mavlm_attn_args {
   // b-1's (K and V alike); lse2 is [H, R].  nb = 1: a single video.
   int nb = 1;
   long long kv_bstride = 0;
+  // variable-length row batch (mavlm_launch_attention3_varlen only): HOST arrays of nb <= MAVLM_VBASE_MAX entries - video b has
+  // vl_S[b] keys that start vl_off[b] elements into K and V; S and kv_bstride are not read
+  const int* vl_S = nullptr;
+  const long long* vl_off = nullptr;
 };
 hipError_t mavlm_launch_attention(const mavlm_attn_args& a, int dtype, hipStream_t s);
+// head_dim <= 128, plain grid, per-video key counts (attention3.hip): the bits of nb plain-grid single launches
+hipError_t mavlm_launch_attention3_varlen(const mavlm_attn_args& a, int dtype, hipStream_t s);
 // the same at head_dim 448 (attention_hd.hip): frame_scr = mavlm_attention_hd_frames_scr_floats floats (one 8-byte entry per query row
 // and 32-key tile), frame_out = mavlm_attention_hd_frames_out_floats floats; a.lse2 required
 bool mavlm_attention_hd_frames_supported(int R, int S, int H, int head_dim, int frame_keys);
@@ -223,7 +229,13 @@ struct mavlm_colsum_args {
   // ([nb][planes][H][S]).  Every video runs the single-video schedule on its own operands: the bits of nb single launches.
   int nb = 1;
   long long kv_bstride = 0, part_bstride = 0;
+  // variable-length row batch (mavlm_launch_colsum3_varlen only): HOST arrays of nb <= MAVLM_VBASE_MAX entries - video b has
+  // vl_S[b] keys that start vl_kv_off[b] elements into K; its planes start sum_{v<b} mavlm_colsum_part_floats(R, vl_S[v], H)
+  // floats into part.  S and the two strides are not read.
+  const int* vl_S = nullptr;
+  const long long* vl_kv_off = nullptr;
 };
+hipError_t mavlm_launch_colsum3_varlen(const mavlm_colsum_args& a, int dtype, hipStream_t s);
 // column-sum pass of the head_dim-128 kernels: workgroups of the balanced schedule / planes of `part` (attention3.hip)
 int mavlm_colsum_plan(int R, int S, int H, int* planes);
 int mavlm_colsum_planes(int R, int S, int H);         // planes the selected kernel writes (1 for the register-staged one)

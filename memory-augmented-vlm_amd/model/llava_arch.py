@@ -455,6 +455,87 @@ def _video_memory_tokens_ragged(model, bp, images, frame_idx_cpu, memory_prompt_
     return [buf[dst[back[i]]:dst[back[i]] + rows[back[i]]] for i in range(k)], info
 
 
+@torch.no_grad()
+def video_memory_tokens_clips(model, bp: BatchedProjector, images, frame_idx_cpu, memory_prompt_embeds: torch.Tensor,
+                              frame_prompt_embeds: torch.Tensor, image_newline: Optional[torch.Tensor], with_frames: bool = True,
+                              chunk: int = 32, fine_frames: int = 32, out: Optional[torch.Tensor] = None,
+                              layout: str = "one_token", dst_rows: Optional[List[int]] = None):
+    """`video_memory_tokens` for k clips (2 <= k <= bp.batch) of 1 <= T_b < `chunk` frames each on one row-batched engine: every
+    clip is ONE chunk of all its frames (llava_arch.py:528), so the k videos take one step together - different frame counts
+    in one step (`BatchedProjector.step_frames`) - and one emit with a fine-frame count per video
+    (`mavlm_fuse_emit_layout_frames_to`; a clip's fine frames are all its frames, :513-522).  Internally the clips are ordered
+    longest first (stable).  `images`: k tensors [T_b, P, D]; `frame_idx_cpu`: one index tensor per clip.  Returns (list of
+    [rows_b, D] blocks in the caller's order - or `out`, a contiguous [out_rows, D] buffer, with `dst_rows` -, info).  Inference."""
+    layout_period(layout, images[0].shape[1])
+    k = len(images)
+    if not 2 <= k <= bp.batch:
+        raise capi.MavlmError(f"video_memory_tokens_clips: 2..{bp.batch} videos expected")
+    P, D = images[0].shape[1:]
+    dev, dt = images[0].device, images[0].dtype
+    for im in images:
+        if not im.is_cuda or im.dim() != 3 or tuple(im.shape[1:]) != (P, D) or im.dtype != dt or im.device != dev:
+            raise capi.MavlmError("video_memory_tokens_clips: GPU frame tokens [T_b, P, D] of one dtype / device expected")
+        if not 1 <= im.shape[0] < chunk:
+            raise capi.MavlmError(f"video_memory_tokens_clips: a clip has 1..{chunk - 1} frames (one chunk of all its frames); "
+                                  f"got {im.shape[0]}")
+    if not isinstance(frame_idx_cpu, (list, tuple)) or len(frame_idx_cpu) != k or \
+            any(i.numel() != im.shape[0] for i, im in zip(frame_idx_cpu, images)):
+        raise capi.MavlmError("video_memory_tokens_clips: one frame index tensor per video, of its length")
+    if D % 256:                                  # (refused before any step: mavlm_fuse_emit_layout_frames_to would, afterwards)
+        raise capi.MavlmError(f"video_memory_tokens_clips: the row-batched emit needs a hidden size that is a multiple of 256; got {D}")
+    pe: TemporalPositionalEncoding = model.positional_encoding
+    rm: TransformerProjector = model.recurrent_memory_transformer
+    order = sorted(range(k), key=lambda i: -images[i].shape[0])            # longest first; stable in the caller's order
+    xs, fines = [], []
+    for i in order:
+        pe.check_indices(frame_idx_cpu[i])
+        xs.append(pe(images[i], _device_indices(frame_idx_cpu[i], dev), indices_checked=True))      # :510-511
+        fines.append(fine_frame_indices(images[i].shape[0], fine_frames))                           # :513-522
+    bp.reset()                                                                                      # :532
+    bp.step_frames(xs)                                                                              # :534-537: one chunk each
+    eng = bp.engine(dev, dt)
+    mp = memory_prompt_embeds.to(dt).contiguous()
+    fp = frame_prompt_embeds.to(dt).contiguous()
+    nl, nl_ptr = _newline_ptr(image_newline, layout, dev, dt)
+    rows = [video_token_rows(x.shape[0], rm.num_memory_tokens, P, with_frames, chunk, fine_frames, eng.c.cache_cap, mp.shape[0],
+                             fp.shape[0], layout) for x in xs]
+    if dst_rows is not None:
+        if out is None or out.dim() != 2 or out.shape[1] != D or out.dtype != dt or not out.is_contiguous() or not out.is_cuda \
+                or len(dst_rows) != k:
+            raise capi.MavlmError(f"video_memory_tokens_clips: `dst_rows` needs {k} rows of a contiguous [out_rows,{D}] {dt} "
+                                  "GPU tensor `out`")
+        buf, dst = out, [int(dst_rows[i]) for i in order]
+    else:
+        if out is not None:
+            raise capi.MavlmError("video_memory_tokens_clips: `out` goes with `dst_rows` (the blocks differ in length)")
+        buf = torch.empty((sum(rows), D), device=dev, dtype=dt)
+        dst = [sum(rows[:j]) for j in range(k)]
+    import ctypes
+    written = (ctypes.c_int64 * k)()
+    xptrs = (capi.vp * k)(*[x.data_ptr() for x in xs])
+    n_fines = [int(f.numel()) for f in fines]
+    fine_ld = max(n_fines) + (max(n_fines) & 1)                              # (even: every index row starts 16-byte aligned)
+    fine_cpu = torch.zeros((k, fine_ld), dtype=torch.long)
+    for j, f in enumerate(fines):
+        fine_cpu[j, :f.numel()] = f
+    fine_dev = _device_indices(fine_cpu.reshape(-1), dev)                    # [k, fine_ld], one row per video
+    capi.check(capi.lib().mavlm_fuse_emit_layout_frames_to(eng.ctx, k, xptrs, fine_dev.data_ptr(), fine_ld, (capi.i32 * k)(*n_fines),
+                                                           mp.data_ptr(), mp.shape[0], fp.data_ptr(), fp.shape[0], nl_ptr,
+                                                           1 if with_frames else 0, capi.LAYOUTS[layout], buf.data_ptr(),
+                                                           buf.shape[0], (ctypes.c_int64 * k)(*dst), written, ops.stream_ptr()),
+               "mavlm_fuse_emit_layout_frames_to")
+    assert list(written) == rows
+    back = [0] * k                               # caller's position -> position in the engine's order
+    for j, i in enumerate(order):
+        back[i] = j
+    info = {"order": order, "num_memories": [1] * k, "pe_frames": [xs[back[i]] for i in range(k)],
+            "fine_idx": [fines[back[i]] for i in range(k)], "block_rows": [rows[back[i]] for i in range(k)],
+            "frame_scores": bp.frame_scores}
+    if dst_rows is not None:
+        return out, info
+    return [buf[dst[back[i]]:dst[back[i]] + rows[back[i]]] for i in range(k)], info
+
+
 def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame_idx_cpu,
                                       memory_prompt_embeds: torch.Tensor, frame_prompt_embeds: torch.Tensor,
                                       image_newline: Optional[torch.Tensor], with_frames: bool = True, chunk: int = 32,
@@ -684,6 +765,55 @@ def plan_ragged_batches(lengths, chunk=32, keys=None, sizes=ROW_BATCH_SIZES):
     return ragged, [[rest[j] for j in b] for b in batches], [rest[j] for j in singles]
 
 
+CLIP_MAX_FRAMES = 32        # a video of fewer frames is ONE chunk of all its frames (sample_frame_count, uniform_segment_variant)
+
+
+def plan_clip_batches(lengths, keys=None, sizes=ROW_BATCH_SIZES):
+    """Which CLIPS of a forward step together (clip row batches: different frame counts in one step).
+    `lengths`: the sampled frame count of each video, in input order; a video is eligible when 0 < length < 32 - it then runs
+    as one chunk of all its frames, and no two such videos of different lengths share a row batch otherwise.  Equal lengths
+    are eligible too (their group takes the equal-F step).  `keys`: as in `plan_ragged_batches`.
+    Eligible videos with one key are sorted by length, longest first, stable in input order.  A video joins the current group
+    while the group has fewer than 8 videos and its length is at least HALF that of the group's longest video; otherwise it
+    opens a new group.  A group of k >= 2 videos runs on ONE row-batched engine: the smallest size in `sizes` that is >= k.
+    The "half" bound keeps the key counts of a variable-length launch within a factor of two (the longest video's workgroups
+    set its duration); like the bound of `plan_ragged_batches` it is a policy picked WITHOUT a measurement
+    (tools/diag_clip_batch.py times one group).
+    Returns (clips, rest): `clips` = [(engine size, positions longest first)], the groups in the order of their first video;
+    `rest` = the positions of every other video, ascending - they go through today's planners."""
+    sizes_up = sorted({int(s) for s in sizes})
+    if any(s < 2 or s > 16 for s in sizes_up):
+        raise ValueError("row batch sizes: 2 .. 16 videos")
+    n = len(lengths)
+    keys = [None] * n if keys is None else list(keys)
+    if len(keys) != n:
+        raise ValueError("plan_clip_batches: one key per video")
+    cap = min(RAGGED_MAX_GROUP, sizes_up[-1]) if sizes_up else 0
+    by_key = {}
+    for i, t in enumerate(lengths):
+        if 0 < int(t) < CLIP_MAX_FRAMES:
+            by_key.setdefault(keys[i], []).append(i)
+    clips, taken = [], set()
+    for members in by_key.values():
+        members = sorted(members, key=lambda i: -int(lengths[i]))            # (stable: input order among equal lengths)
+        groups, cur = [], []
+        for i in members:
+            if cur and len(cur) < cap and 2 * int(lengths[i]) >= int(lengths[cur[0]]):
+                cur.append(i)
+            else:
+                if cur:
+                    groups.append(cur)
+                cur = [i]
+        if cur:
+            groups.append(cur)
+        for g in groups:
+            if len(g) >= 2:
+                clips.append((next(s for s in sizes_up if s >= len(g)), g))
+                taken.update(g)
+    clips.sort(key=lambda sg: min(sg[1]))
+    return clips, [i for i in range(n) if i not in taken]
+
+
 class VideoPlacement:
     """Where everything of a batch of samples lands in the padded [B, Lmax, D] `inputs_embeds` buffer when each video block is
     emitted in place - what `splice_into_text` arrives at by concatenating and padding, computed on the host from the token ids
@@ -771,7 +901,8 @@ def features_per_sample(video_of, tokens):
 
 
 def run_video_groups(model, videos, mem_prompt, frame_prompt, image_newline, with_frames=True, layout="one_token",
-                     sizes=ROW_BATCH_SIZES, train=False, out=None, dst_rows=None, single=None, ragged=False, ragged_train=False):
+                     sizes=ROW_BATCH_SIZES, train=False, out=None, dst_rows=None, single=None, ragged=False, ragged_train=False,
+                     clips=False):
     """The memory path for several videos on the current stream - the ONE place that groups videos into row batches.
     `videos`: (pooled frame tokens [T, P, D], original frame indices [T] on the host) per video.  Videos with the same sampled
     frame count, dtype and device form a group (they share chunk bounds and fine-frame indices); `plan_row_batches` cuts it into
@@ -786,8 +917,30 @@ def run_video_groups(model, videos, mem_prompt, frame_prompt, image_newline, wit
     in one row batch, one ragged emit per group (`video_memory_tokens_batched(ragged=True)`); the rest as above.
     `ragged_train` (enable_ragged_row_batches(on, training=True)): with `train` the grouping comes from `plan_ragged_batches`
     too (same policy, same sizes) and a group runs through `video_memory_tokens_ragged_train`; without `train` it
-    changes nothing."""
+    changes nothing.
+    `clips` (LlavaMetaForCausalLM.enable_clip_row_batches; inference - under autograd it changes nothing): the videos of fewer
+    than 32 sampled frames are grouped by `plan_clip_batches` first - different frame counts in ONE step, one emit per group
+    (`video_memory_tokens_clips`); every other video goes through the grouping above."""
     rm = model.recurrent_memory_transformer
+    if clips and not train:
+        cgroups, rest = plan_clip_batches([v[0].shape[0] for v in videos], [(v[0].dtype, str(v[0].device)) for v in videos], sizes)
+        if cgroups:
+            tokens = [None] * len(videos)
+            for size, grp in cgroups:
+                toks = video_memory_tokens_clips(model, rm.row_batcher(size), [videos[i][0] for i in grp], [videos[i][1] for i in grp],
+                                                 mem_prompt, frame_prompt, image_newline, with_frames, out=out, layout=layout,
+                                                 dst_rows=None if out is None else [dst_rows[i] for i in grp])[0]
+                if out is None:
+                    for j, i in enumerate(grp):
+                        tokens[i] = toks[j]
+            sub = run_video_groups(model, [videos[i] for i in rest], mem_prompt, frame_prompt, image_newline, with_frames, layout,
+                                   sizes, train, out, None if out is None else [dst_rows[i] for i in rest], single, ragged,
+                                   ragged_train) if rest else []
+            if out is not None:
+                return None
+            for j, i in enumerate(rest):
+                tokens[i] = sub[j]
+            return tokens
     groups = []
     if (ragged and not train) or (ragged_train and train):
         groups, batches, singles = plan_ragged_batches([v[0].shape[0] for v in videos], 32,
@@ -1242,7 +1395,8 @@ class LlavaMetaForCausalLM:
         if train or plan.general or not vids[0][0].is_cuda or any(p.device != dev or p.dtype != dt for p, _ in vids):
             tokens = run_video_groups(model, vids, mem_prompt, frame_prompt, newline, not drop, layout, self.row_batch_sizes,
                                       train=train, ragged=self._ragged_row_batches and not train,
-                                      ragged_train=self._ragged_row_batches_train and train)
+                                      ragged_train=self._ragged_row_batches_train and train,
+                                      clips=self._clip_row_batches and not train)
             return splice_into_text(self, model, features_per_sample(plan.video_of, tokens), input_ids, position_ids,
                                     attention_mask, past_key_values, labels)
         # in place: the padded buffer once, text rows from embed_tokens, padding zeroed, every block emitted where it belongs
@@ -1257,7 +1411,8 @@ class LlavaMetaForCausalLM:
             at += hi - lo
         with torch.no_grad():
             run_video_groups(model, vids, mem_prompt, frame_prompt, newline, not drop, layout, self.row_batch_sizes,
-                             out=emb.view(B * L, D), dst_rows=plan.dst_row, ragged=self._ragged_row_batches)
+                             out=emb.view(B * L, D), dst_rows=plan.dst_row, ragged=self._ragged_row_batches,
+                             clips=self._clip_row_batches)
         if text is not None and text.dtype != dt:
             emb = emb.to(text.dtype)
         lab_list = None if labels is None else [l[m] for l, m in zip(labels, mask)]
@@ -1280,6 +1435,19 @@ class LlavaMetaForCausalLM:
         per step; `on=False` switches both off."""
         self._ragged_row_batches = bool(on)
         self._ragged_row_batches_train = bool(on) and bool(training)
+
+    _clip_row_batches = False
+
+    def enable_clip_row_batches(self, on: bool = True):
+        """Several videos per forward: let the videos of FEWER than 32 frames share a row batch (off by default).  Such a video
+        is one chunk of all its frames, so two of them step together only when their frame counts are equal; everything else
+        runs as single videos.  On, they are grouped by `plan_clip_batches`: up to 8 clips whose lengths differ by at most a
+        factor of two share one row-batched engine and take ONE step with a frame count per video (`mavlm_step_batch_frames`),
+        then one emit per group into the padded `inputs_embeds`.  Inference only: a forward that records a graph keeps the
+        grouping of the switch off.  Independent of `enable_ragged_row_batches` (which serves the videos of 32 frames and more).
+        Like every row-batched emit it needs a hidden size that is a multiple of 256 (D = 896: `MavlmError` from the emit).
+        Measured 1.23 x at D = 1024 and 0.96 x (slower) at D = 3584 with 4 clips: hence off by default."""
+        self._clip_row_batches = bool(on)
 
     # -- hipGraph replay for repeated video shapes (round 4) -------------------------------------------------------------
     def enable_memory_graphs(self, capacity: int = 4):

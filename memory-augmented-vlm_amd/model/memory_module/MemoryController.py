@@ -851,6 +851,47 @@ class BatchedProjector:
             self.frame_scores.append(scores)
         return scores
 
+    @torch.no_grad()
+    def step_frames(self, segs):
+        """`step` for chunks that differ in their FIRST dimension (`mavlm_step_batch_frames`): segs = k tensors [F_b, P, D], the
+        clips of fewer than 32 frames whose single chunk holds all their frames.  The same prefix rule as `step`.  Returns a list
+        of k [F_b] views into one padded [k, Fmax] tensor, which is appended to `frame_scores` (the entries behind a video's F_b
+        are zeros the step never writes).  Equal F_b take the launches and the bits of `step`.  No attention maps."""
+        k = len(segs)
+        if (self._active == 0 and not 2 <= k <= self.batch) or (self._active and not 1 <= k <= self._active):
+            raise capi.MavlmError(f"BatchedProjector.step_frames: 2..{self.batch} chunks at the first step of a batch, then no "
+                                  f"more than the step before ({self._active or self.batch}); got {k}")
+        P, D = segs[0].shape[1:]
+        for t in segs:
+            if not t.is_cuda or t.dim() != 3 or tuple(t.shape[1:]) != (P, D) or t.shape[0] < 1 or not t.is_contiguous() or \
+                    t.dtype != segs[0].dtype:
+                raise capi.MavlmError("BatchedProjector.step_frames: contiguous GPU chunks [F_b, P, D] of one dtype expected")
+        if P != self.proj.patch_size or D != self.proj.hidden_size:
+            raise capi.MavlmError(f"expected [F,{self.proj.patch_size},{self.proj.hidden_size}] chunks")
+        if self._mode == "autograd":
+            raise capi.MavlmError("BatchedProjector.step_frames: this video batch holds autograd tensors of `step_train`: "
+                                  "`reset()` before running the inference step")
+        if self.record_attention_maps:
+            raise capi.MavlmError("BatchedProjector.step_frames: attention maps of chunks with different frame counts are not provided")
+        self._mode = "engine"
+        Fs = [int(t.shape[0]) for t in segs]
+        Fmax = max(Fs)
+        eng = self.engine(segs[0].device, segs[0].dtype, Fmax)
+        eng.set_maps(False)
+        ptrs = (capi.vp * k)(*[t.data_ptr() for t in segs])
+        fv = (capi.i32 * k)(*Fs)
+        scores = torch.zeros((k, Fmax), device=segs[0].device, dtype=segs[0].dtype) if self.compute_frame_scores else None
+        capi.check(capi.lib().mavlm_step_batch_frames(eng.ctx, ptrs, fv, k, scores.data_ptr() if scores is not None else 0, Fmax, 0,
+                                                      ops.stream_ptr()), "mavlm_step_batch_frames")
+        self._n += 1
+        self._active = k
+        for b in range(k):
+            self._vsteps[b] += 1
+        if scores is None:
+            return None
+        self.frame_scores.append(scores)
+        return [scores[b, :Fs[b]] for b in range(k)]
+
     def step_train(self, segs, ragged=False):
         """One chunk of every video under autograd (see the class docstring): segs = B tensors [F, P, D] of one shape.  Mirrors
         `TransformerProjector._forward_autograd` over the stacked rows, in the launch order of `mavlm_step_batch`.  Returns the
