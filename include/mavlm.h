@@ -264,7 +264,11 @@ int mavlm_fuse_emit_layout(mavlm_ctx* ctx, const void* x_pe, const int64_t* fine
                            int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt, const void* newline,
                            int32_t with_frames, int32_t layout, void* out, int64_t out_capacity_rows, int64_t* rows,
                            void* stream);
-/* mavlm_fuse_emit_batch with a layout (same reference lines; one video per forward there, llava_arch.py:436) */
+/* mavlm_fuse_emit_batch with a layout (same reference lines; one video per forward there, llava_arch.py:436).
+ * Hidden sizes: every multiple of 128 (this export, mavlm_fuse_emit_layout_batch_to and mavlm_fuse_emit_layout_ragged_to).  At a
+ * multiple of 256 the fuser's second GEMM scatters its rows on the 256-column-tile kernels; at the others (D = 896, 384 ...) on
+ * the row-mapped form of the 128 x 128 kernel, which addresses `out` with 32-bit byte offsets: MAVLM_E_SHAPE, before anything
+ * is enqueued, when the furthest block ends 4 GiB - 256 bytes or more into `out`. */
 int mavlm_fuse_emit_layout_batch(mavlm_ctx* ctx, const void* const* x_pe, const int64_t* fine_idx, int32_t n_fine,
                                  const void* mem_prompt, int32_t n_mem_prompt, const void* frame_prompt, int32_t n_frame_prompt,
                                  const void* newline, int32_t with_frames, int32_t layout, void* out, int64_t rows_per_video,
@@ -306,7 +310,8 @@ int mavlm_fuse_emit_layout_ragged_to(mavlm_ctx* ctx, int32_t n_videos, const voi
  * The same code: mavlm_fuse_emit_layout_ragged_to is this call with a constant count and fine_ld = n_fine (the same launches, the
  * same bits); with different counts the literal rows and the fine frames run once per range of consecutive videos with one
  * count.  The bounds and disjointness checks are made by each block's own length, before anything is enqueued.  MAVLM_E_SHAPE:
- * a hidden size that is no multiple of 256 (the row map of the fuser's second GEMM; refused here before anything is enqueued). */
+ * a hidden size that is no multiple of 256, refused here before anything is enqueued.  This is the one row-batched emit that
+ * keeps that limit (the equal-count exports above take every multiple of 128): clip row batches stay refused at D = 896. */
 int mavlm_fuse_emit_layout_frames_to(mavlm_ctx* ctx, int32_t n_videos, const void* const* x_pe, const int64_t* fine_idx,
                                      int64_t fine_ld, const int32_t* n_fine, const void* mem_prompt, int32_t n_mem_prompt,
                                      const void* frame_prompt, int32_t n_frame_prompt, const void* newline, int32_t with_frames,

@@ -24,13 +24,25 @@ constexpr int GEMM_LDS = 2 * STAGE_BYTES;      // 64 KiB
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
-template <typename T, int EPI>
+// Output-row map of the bias epilogue (mavlm_gemm_args::c_rpb / c_gap / c_vbase), for the row-batched emits at widths the
+// 256-column-tile kernels do not take (N % 256 != 0).  MAP, GAP and VB are template parameters: an instantiation without the
+// map takes two empty arguments, reads nothing of them and is the kernel it was.  `bytes`: the furthest mapped byte + 1 (the
+// launcher computes it and refuses a launch that would pass MAP_DROP).
+template <bool MAP> struct rowmap_arg {};
+template <> struct rowmap_arg<true> {
+  int rpb, nb, gap;
+  unsigned bytes;
+  long long bstride;
+};
+constexpr uint32_t MAP_DROP = (uint32_t)MAVLM_GEMM_MAP_REACH;     // byte offset of a row that must not be stored: past every descriptor's end
+
+template <typename T, int EPI, bool MAP = false, bool GAP = false, bool VB = false>
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const uint16_t* __restrict__ A, int lda,
                                                          const uint16_t* __restrict__ W, int ldw,
                                                          const float* __restrict__ bias,
                                                          const uint16_t* __restrict__ res, int ldr,
                                                          void* __restrict__ Cout, int ldc, int M, int N, int K,
-                                                         int ksplit) {
+                                                         int ksplit, rowmap_arg<MAP> rm, mavlm_vbase_arg<VB> vb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // split-K (backward dW = dY^T X, contraction over tens of thousands of rows with only (N/128)^2 output tiles):
   // blockIdx.y owns K range [y*ksplit, (y+1)*ksplit) and its own fp32 partial plane (EPI_F32 only)
@@ -147,8 +159,32 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const uint16_t* __restr
     const uintptr_t a = (uintptr_t)Cout;
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
     const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    const uint32_t bytes = __builtin_amdgcn_readfirstlane(((uint32_t)(M - 1) * (uint32_t)ldc + (uint32_t)N) * (uint32_t)ESZ);
+    uint32_t bytes = __builtin_amdgcn_readfirstlane(((uint32_t)(M - 1) * (uint32_t)ldc + (uint32_t)N) * (uint32_t)ESZ);
+    if constexpr (MAP) bytes = rm.bytes;
     crs = __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | lo), 0, bytes, 0x00020000);
+  }
+  // Row map (the formula of gemm256.hip's crow): block q = m / rpb of rpb rows goes to batch element q % nb as its
+  // (q / nb)-th block, at vb.off[b] (VB) or b * bstride; GAP: row v of a batch element lands v / gap rows further down.  The
+  // lane's 4 row offsets (bytes, its first column included) are computed here, once, ahead of the first store - the read of the
+  // argument block included.  A row m >= M of a ragged last tile is no longer past the descriptor's end (q runs on and q % nb
+  // wraps into another video's block): it gets MAP_DROP, an offset past the end of every descriptor the launcher makes, so
+  // the hardware drops it and the store loop stays branch-free.
+  uint32_t ro[4];
+  if constexpr (MAP) {
+    const uint32_t cb = (uint32_t)(n0 + wn * 64 + fq * 4) * 2u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = m0 + wm * 64 + i * 16 + fr;
+      const int mc = m < M ? m : M - 1;
+      const int q = mc / rm.rpb, r = mc - q * rm.rpb;
+      const int qb = q / rm.nb, b = q - qb * rm.nb;
+      const int v = qb * rm.rpb + r;
+      size_t e;
+      if constexpr (VB) e = (size_t)vb.off[b];
+      else e = (size_t)b * (size_t)rm.bstride;
+      e += (size_t)(GAP ? v + v / rm.gap : v) * ldc;
+      ro[i] = m < M ? (uint32_t)e * 2u + cb : MAP_DROP;
+    }
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -156,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const uint16_t* __restr
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int n = n0 + wn * 64 + j * 16 + fq * 4;
-      const int off = (m * ldc + n) * ESZ;
+      const int off = MAP ? (int)(ro[i] + (uint32_t)j * 32u) : (m * ldc + n) * ESZ;
       float v0 = acc[i][j][0] + bv[j][0], v1 = acc[i][j][1] + bv[j][1], v2 = acc[i][j][2] + bv[j][2],
             v3 = acc[i][j][3] + bv[j][3];
       if (EPI == MAVLM_EPI_RELU) {
@@ -189,8 +225,46 @@ hipError_t launch(const mavlm_gemm_args& g, hipStream_t s) {
   }
   const int ntm = (g.M + BM - 1) / BM, ntn = g.N / BN;
   hipLaunchKernelGGL(kern, dim3(ntm * ntn), dim3(256), GEMM_LDS, s, (const uint16_t*)g.A, g.lda, (const uint16_t*)g.W,
-                     g.ldw, g.bias, (const uint16_t*)g.res, g.ldr, g.C, g.ldc, g.M, g.N, g.K, 0);
+                     g.ldw, g.bias, (const uint16_t*)g.res, g.ldr, g.C, g.ldc, g.M, g.N, g.K, 0, rowmap_arg<false>{},
+                     mavlm_vbase_arg<false>{});
   return hipGetLastError();
+}
+
+// The row-mapped bias-epilogue launch (row-batched output, c_rpb > 0; mavlm_launch_gemm has checked the block counts and the
+// alignment).  The buffer stores keep their 32-bit byte offsets, so the furthest byte a video's rows can reach - the largest
+// base + the rows of one video in this launch, gaps included, * ldc - has to lie below MAP_DROP: refused otherwise, no wrap.
+template <typename T, bool GAP, bool VB>
+hipError_t launch_mapped(const mavlm_gemm_args& g, hipStream_t s) {
+  const long long rows_v = (long long)(g.M / g.c_rpb / g.c_nb) * g.c_rpb;                  // rows of one video in this launch
+  const long long last = rows_v - 1 + (GAP ? (rows_v - 1) / g.c_gap : 0);                  // its last row, gaps included
+  long long base = 0;
+  for (int b = 0; b < g.c_nb; ++b) {
+    const long long o = VB ? g.c_vbase[b] : (long long)b * g.c_bstride;
+    if (o < 0) return hipErrorInvalidValue;
+    base = o > base ? o : base;
+  }
+  if (g.ldc < g.N || ((double)base + (double)(last + 1) * g.ldc) * 2.0 >= (double)MAP_DROP) return hipErrorInvalidValue;
+  rowmap_arg<true> rm;
+  rm.rpb = g.c_rpb; rm.nb = g.c_nb; rm.gap = g.c_gap; rm.bstride = g.c_bstride;
+  rm.bytes = (unsigned)((base + last * g.ldc + g.N) * 2);
+  mavlm_vbase_arg<VB> vb = {};
+  if constexpr (VB) vb = mavlm_vbase_pack(g.c_vbase, g.c_nb);
+  auto kern = gemm_tn_kernel<T, MAVLM_EPI_BIAS, true, GAP, VB>;
+  static mavlm_per_device_once once;   // per instantiation
+  {
+    hipError_t e = once.dyn_lds((const void*)kern, GEMM_LDS);
+    if (e != hipSuccess) return e;
+  }
+  const int ntm = (g.M + BM - 1) / BM, ntn = g.N / BN;
+  hipLaunchKernelGGL(kern, dim3(ntm * ntn), dim3(256), GEMM_LDS, s, (const uint16_t*)g.A, g.lda, (const uint16_t*)g.W,
+                     g.ldw, g.bias, (const uint16_t*)nullptr, 0, g.C, g.ldc, g.M, g.N, g.K, 0, rm, vb);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_mapped_form(const mavlm_gemm_args& g, hipStream_t s) {
+  if (g.c_vbase) return g.c_gap > 0 ? launch_mapped<T, true, true>(g, s) : launch_mapped<T, false, true>(g, s);
+  return g.c_gap > 0 ? launch_mapped<T, true, false>(g, s) : launch_mapped<T, false, false>(g, s);
 }
 
 template <typename T>
@@ -204,7 +278,8 @@ hipError_t launch_splitk(const mavlm_gemm_args& g, int splits, int ksplit, hipSt
   }
   const int ntm = (g.M + BM - 1) / BM, ntn = g.N / BN;
   hipLaunchKernelGGL(kern, dim3(ntm * ntn, splits), dim3(256), GEMM_LDS, s, (const uint16_t*)g.A, g.lda,
-                     (const uint16_t*)g.W, g.ldw, g.bias, (const uint16_t*)nullptr, 0, g.C, g.ldc, g.M, g.N, g.K, ksplit);
+                     (const uint16_t*)g.W, g.ldw, g.bias, (const uint16_t*)nullptr, 0, g.C, g.ldc, g.M, g.N, g.K, ksplit,
+                     rowmap_arg<false>{}, mavlm_vbase_arg<false>{});
   return hipGetLastError();
 }
 
@@ -322,7 +397,7 @@ size_t mavlm_gemm_split_ws_floats(int M, int N, int K, int epilogue, int ldc) {
 
 bool mavlm_gemm_row_map_ok(const mavlm_gemm_args& g) {
   if (g.epilogue == MAVLM_EPI_LN) return false;
-  if (g.c_rpb > 0) return true;               // (row-batched outputs only ever run on the 256-column-tile kernels)
+  if (g.c_rpb > 0) return true;               // (row-batched outputs only ever run on a kernel with the map: mavlm_launch_gemm)
   if (g.splitk_ws != nullptr && g_mavlm_gemm_tile == 0 && mavlm_gemm_splits(g.M, g.N, g.K, g.epilogue, g.ldc) > 1) return false;
   return use_128x256(g) || use_256(g);
 }
@@ -351,14 +426,20 @@ hipError_t mavlm_launch_gemm(const mavlm_gemm_args& g, int dtype, hipStream_t s)
     return mavlm_launch_gemm256(g, dtype, s);
   }
   if (g.c_rpb > 0) {
-    // row-batched output: only the 256-column-tile kernels scatter their rows (the stacked rows of several videos fill
-    // the chip - there is no small-grid case to serve)
+    // row-batched output: the 256-column-tile kernels scatter their rows (the stacked rows of several videos fill the chip -
+    // there is no small-grid case to serve); a width they do not take, N % 256 != 0 with N % 128 == 0 (hidden 896: the
+    // fuser's second GEMM), runs on the row-mapped form of the 128^2 kernel - the bias epilogue only.  The tile hook has
+    // nothing to choose there.
     if (g.M % g.c_rpb != 0 || g.c_nb < 1 || (g.M / g.c_rpb) % g.c_nb != 0 || (g.c_bstride & 7) || g.epilogue == MAVLM_EPI_RES_F32 ||
-        !mavlm_gemm256_supported(g) || ((uintptr_t)g.C & 15) || (g.ldc & 7) || (g.lda & 7) || (g.ldw & 7))
+        ((uintptr_t)g.C & 15) || (g.ldc & 7) || (g.lda & 7) || (g.ldw & 7))
+      return hipErrorInvalidValue;
+    const bool narrow = g.N % 256 != 0;
+    if (narrow ? (g.N % BN != 0 || g.K % BK != 0 || g.K <= 0 || g.epilogue != MAVLM_EPI_BIAS) : !mavlm_gemm256_supported(g))
       return hipErrorInvalidValue;
     const double osz = g.epilogue == MAVLM_EPI_F32 ? 4.0 : 2.0;
     mavlm_prof_scope prof(MAVLM_K_GEMM, 2.0 * g.M * (double)g.N * g.K,
                           2.0 * ((double)g.M * g.K + (double)g.N * g.K) + osz * g.M * (double)g.N, s);
+    if (narrow) return dtype == MAVLM_F16 ? launch_mapped_form<F16>(g, s) : launch_mapped_form<BF16>(g, s);
     if (use_128x256(g)) return mavlm_launch_gemm128(g, dtype, s);
     const int rows = mavlm_gemm_tile_rows(g.M, g.N);
     const long tiles = (long)((g.M + rows - 1) / rows) * (g.N / 256);

@@ -152,7 +152,7 @@ mavlm_gemm_args fuser_out_gemm(const mavlm_config& c, int rows, void* C, float* 
 // take the 128^2 kernel or the split-K reduce - writers of M x N contiguous elements - write here instead and one copy
 // kernel places the rows: the bytes of the largest such launch (0 = every launch of this config maps its rows).
 size_t fuse_stage_bytes(const mavlm_config& c, int fuse_mems, size_t gsplit_floats) {
-  if (nbatch(c) > 1) return 0;                      // (a row batch only ever runs the 256-column-tile kernels)
+  if (nbatch(c) > 1) return 0;                      // (a row batch only ever runs kernels with the row map)
   size_t rows_max = 0;
   for (int run = 1; run <= fuse_mems; ++run) {
     const int rows = run * c.mem_tokens * c.patches;
@@ -1189,6 +1189,16 @@ int fuse_emit_impl(mavlm_ctx* x, const void* const* x_pe, const int64_t* fine_id
     }
     vbase = vbase_;
   }
+  // a row batch at a hidden size the 256-column-tile kernels do not take: the fuser's second GEMM maps its rows with 32-bit byte
+  // offsets (MAVLM_GEMM_MAP_REACH) - a destination that reaches further is refused here, before the first launch
+  if (B > 1 && D % 256 != 0) {
+    int64_t top = (int64_t)(B - 1) * cap_rows + need;
+    if (dst_row) {
+      top = 0;
+      for (int b = 0; b < B; ++b) top = dst_row[b] + need > top ? dst_row[b] + need : top;
+    }
+    if ((double)top * D * 2.0 >= (double)MAVLM_GEMM_MAP_REACH) return MAVLM_E_SHAPE;
+  }
   if (with_frames && n_fine)
     for (int b = 0; b < B; ++b)
       if (!x_pe[b]) return MAVLM_E_ARG;
@@ -1299,7 +1309,8 @@ int ragged_emit_impl(mavlm_ctx* x, int nv, const void* const* x_pe, const int64_
     if (nf[b] > n_fine) n_fine = nf[b];                          // (from here on: the largest count)
   }
   if (!n_fine_v) fine_ld = n_fine;
-  // (the fuser's second GEMM writes through the row map of the 256-column-tile kernels: the new export says so up front)
+  // (the per-video fine-frame counts stay with the row map of the 256-column-tile kernels: this export says so up front - the
+  // equal-count exports also run at hidden sizes that are multiples of 128 only, on the row-mapped form of the 128^2 kernel)
   if (n_fine_v && D % 256 != 0) return MAVLM_E_SHAPE;
   if (n_mem_prompt < 0 || n_frame_prompt < 0 || n_fine < 0 || (n_mem_prompt && !mem_prompt) ||
       (with_frames && ((n_frame_prompt && !frame_prompt) || (n_fine && (!x_pe || !fine_idx)))))
@@ -1324,6 +1335,9 @@ int ragged_emit_impl(mavlm_ctx* x, int nv, const void* const* x_pe, const int64_
     for (int a = 0; a < b; ++a)
       if (dst_row[a] < dst_row[b] + need[b] && dst_row[b] < dst_row[a] + need[a]) return MAVLM_E_ARG;
   }
+  if (D % 256 != 0)            // (the 32-bit byte offsets of the narrow-width row map, as in fuse_emit_impl: before the first launch)
+    for (int b = 0; b < nv; ++b)
+      if ((double)(dst_row[b] + need[b]) * D * 2.0 >= (double)MAVLM_GEMM_MAP_REACH) return MAVLM_E_SHAPE;
   if (!x->has_w || !x->has_b) return MAVLM_E_STATE;
   if (!x->w.w_f1 || !x->w.b_f1 || !x->w.w_f2 || !x->w.b_f2_type0 || (with_frames && !x->w.type1)) return MAVLM_E_STATE;
   for (int b = 0; b < nv; ++b) {

@@ -30,13 +30,14 @@ struct mavlm_gemm_args {
   int planes_only = 0;           // split-K: leave the fp32 planes in splitk_ws, no reduction (the caller reduces: dense + LayerNorm);
                                  // *planes_out (if set) receives the number of planes, 0 when the shape takes no split
   int* planes_out = nullptr;
-  // Row-batched output (256-column-tile kernels only; 0 = plain [M, ldc] output): the M rows are blocks of c_rpb rows; block
+  // Row-batched output (0 = plain [M, ldc] output; the 256-column-tile kernels, and for N % 256 != 0 with N % 128 == 0 and the
+  // bias epilogue the row-mapped form of the 128^2 kernel, MAVLM_GEMM_MAP_REACH below): the M rows are blocks of c_rpb rows; block
   // q goes to batch element b = q % c_nb as its (q / c_nb)-th block, i.e. row m lands at
   // C + b * c_bstride + ((q / c_nb) * c_rpb + m % c_rpb) * ldc (elements).  Used where the stacked rows of several videos
   // (mavlm_config::batch) are written to per-video buffers: the evolution K/V ring, the fused-token blocks.
   int c_rpb = 0, c_nb = 1;
   long long c_bstride = 0;
-  // Gapped output rows (256-column-tile kernels, bias epilogue; 0 = none): row v of the [M, ldc] output - of a batch element's
+  // Gapped output rows (bias epilogue; 0 = none; with c_rpb == 0 the 256-column-tile kernels only): row v of the [M, ldc] output - of a batch element's
   // own output when c_rpb > 0 - lands v / c_gap rows further down, i.e. one row is left free after every c_gap rows: the
   // image_newline rows of the `grid` / `frame` video token layouts (llava_arch.py:330-357), which mavlm_launch_copy_rows
   // writes.  Same tiles and same arithmetic as c_gap = 0: only the destination differs.  A launch that mavlm_launch_gemm
@@ -51,6 +52,11 @@ struct mavlm_gemm_args {
 // The per-video bases as a kernel argument: an instantiation that takes none (VB = false, every kernel that existed before the
 // bases) gets an empty argument and the parameter list it had.
 #define MAVLM_VBASE_MAX 16
+// The row-mapped form of the 128^2 kernel (gemm.hip; row-batched bias-epilogue launches with N % 256 != 0) addresses its output
+// with 32-bit byte offsets from C: the furthest byte a launch maps - the largest base + the rows of one video in the launch, gaps
+// included, * ldc - must lie below this, else mavlm_launch_gemm refuses (hipErrorInvalidValue).  Callers that launch anything
+// before that GEMM check their whole destination against it up front.
+#define MAVLM_GEMM_MAP_REACH 0xFFFFFF00ull
 template <bool VB> struct mavlm_vbase_arg {};
 template <> struct mavlm_vbase_arg<true> { long long off[MAVLM_VBASE_MAX]; };
 inline mavlm_vbase_arg<true> mavlm_vbase_pack(const long long* v, int n) {
@@ -63,8 +69,9 @@ bool mavlm_gemm_ln_supported(int M, int N, int K, int wide = -1);
 extern int g_mavlm_gemm_ln_wide;
 size_t mavlm_gemm_ln_ws_bytes(int M, int N);
 hipError_t mavlm_launch_gemm(const mavlm_gemm_args& g, int dtype, hipStream_t s);
-// does mavlm_launch_gemm run this launch (c_gap aside) on a kernel that maps its output rows - the 256-column-tile kernels -
-// rather than on the 128^2 kernel or through the split-K reduce, which write M x N contiguous elements?  Pure function of
+// does mavlm_launch_gemm run this launch (c_gap aside) on a kernel that maps its output rows - the 256-column-tile kernels, or
+// for a row-batched output (c_rpb > 0) the row-mapped form of the 128^2 kernel - rather than on the plain 128^2 kernel or
+// through the split-K reduce, which write M x N contiguous elements?  Pure function of
 // the arguments and the tuning hooks, like the dispatch itself.
 bool mavlm_gemm_row_map_ok(const mavlm_gemm_args& g);
 // split-K plan for GEMMs with few output tiles and a long contraction (small M, K >= 2048): 1 = none.  Pure function of

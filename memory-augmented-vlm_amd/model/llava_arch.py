@@ -482,7 +482,7 @@ def video_memory_tokens_clips(model, bp: BatchedProjector, images, frame_idx_cpu
             any(i.numel() != im.shape[0] for i, im in zip(frame_idx_cpu, images)):
         raise capi.MavlmError("video_memory_tokens_clips: one frame index tensor per video, of its length")
     if D % 256:                                  # (refused before any step: mavlm_fuse_emit_layout_frames_to would, afterwards)
-        raise capi.MavlmError(f"video_memory_tokens_clips: the row-batched emit needs a hidden size that is a multiple of 256; got {D}")
+        raise capi.MavlmError(f"video_memory_tokens_clips: the clip emit needs a hidden size that is a multiple of 256; got {D}")
     pe: TemporalPositionalEncoding = model.positional_encoding
     rm: TransformerProjector = model.recurrent_memory_transformer
     order = sorted(range(k), key=lambda i: -images[i].shape[0])            # longest first; stable in the caller's order
@@ -1445,7 +1445,8 @@ class LlavaMetaForCausalLM:
         factor of two share one row-batched engine and take ONE step with a frame count per video (`mavlm_step_batch_frames`),
         then one emit per group into the padded `inputs_embeds`.  Inference only: a forward that records a graph keeps the
         grouping of the switch off.  Independent of `enable_ragged_row_batches` (which serves the videos of 32 frames and more).
-        Like every row-batched emit it needs a hidden size that is a multiple of 256 (D = 896: `MavlmError` from the emit).
+        The other row-batched emits take every hidden size that is a multiple of 128; the clip emit (a fine-frame count per
+        video, `mavlm_fuse_emit_layout_frames_to`) still needs a multiple of 256 (D = 896: `MavlmError` before any step).
         Measured 1.23 x at D = 1024 and 0.96 x (slower) at D = 3584 with 4 clips: hence off by default."""
         self._clip_row_batches = bool(on)
 
