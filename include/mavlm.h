@@ -26,6 +26,7 @@ extern "C" {
 #define MAVLM_ABI_VERSION 3
 #define MAVLM_MAX_DEPTH 8
 #define MAVLM_MAX_BATCH 64
+#define MAVLM_MAX_HIDDEN 4096   /* widest hidden size: the widest row of the LayerNorm kernels, forward and backward */
 
 #define MAVLM_E_ARG (-1)        /* null pointer / bad size */
 #define MAVLM_E_SHAPE (-2)      /* shape not supported by the kernels */
@@ -36,7 +37,8 @@ typedef struct mavlm_ctx mavlm_ctx;
 /* Hyper-parameters: `Config` (llava/model/memory_module/MemoryController.py:7-18) as overridden at
  * llava/model/llava_arch.py:117-129, plus the FIFO cap (MemoryController.py:153-154). */
 typedef struct mavlm_config {
-  int32_t hidden;           /* D, mm_hidden_size; multiple of 128; head_dim = D/heads <= 128 (D = 896, 1024 ...) or 448 (D = 3584) */
+  int32_t hidden;           /* D, mm_hidden_size; multiple of 128, at most MAVLM_MAX_HIDDEN (wider: MAVLM_E_SHAPE from mavlm_create);
+                             * head_dim = D/heads <= 128 (D = 896, 1024 ...) or 448 (D = 3584) */
   int32_t heads;            /* H, mm_num_attention_heads (8) */
   int32_t patches;          /* P, patch_size (196) */
   int32_t mem_tokens;       /* M, num_memory_tokens (8) */
@@ -493,6 +495,12 @@ int mavlm_attention_group_mass(const void* Q, int32_t ldq, const void* K, int32_
  * MemoryController.py:24,26-28 */
 int mavlm_layernorm(const float* x, const void* res, int32_t ldr, const float* gamma, const float* beta, void* out,
                     int32_t rows, int32_t D, float eps, int32_t dtype, void* stream);
+/* Host only: the kernel form mavlm_layernorm runs for rows of D columns over a residual of row stride ldr (0: no residual) -
+ * the function its dispatch switches on.  100 + c: a wave per row, 8-element chunks, c = 1 / 2 / 4 chunks per lane (D <= 512 /
+ * 1024 / 2048); 200: a workgroup per row (2048 < D <= MAVLM_MAX_HIDDEN); 300 + v: the 4-element fallback (D % 8 == 4 or
+ * ldr % 8 == 4), v = 1 / 2 / 4 / 8 / 16 float4 per lane (D <= 256 v); 0: refused - D % 4 != 0, ldr % 4 != 0 or
+ * D > MAVLM_MAX_HIDDEN, for which mavlm_layernorm returns MAVLM_E_ARG and writes nothing. */
+int mavlm_layernorm_form(int32_t D, int32_t ldr);
 /* out[t,p,:] = x[src[t],p,:] + table[idx[t],:] (src/idx may be null).  position_encoding.py:64; llava_arch.py:524,554 */
 int mavlm_row_add(const void* x, const int64_t* src, const void* table, const int64_t* idx, void* out, int32_t T,
                   int32_t P, int32_t D, int32_t dtype, void* stream);

@@ -112,6 +112,7 @@ SIGNATURES = {
     "mavlm_attention_maps_floats": (C.c_int64, [C.POINTER(Config)]),
     "mavlm_bind_attention_maps": (C.c_int, [vp, vp, C.c_int64]),
     "mavlm_layernorm": (C.c_int, [vp, vp, i32, vp, vp, vp, i32, i32, C.c_float, i32, vp]),
+    "mavlm_layernorm_form": (C.c_int, [i32, i32]),
     "mavlm_row_add": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "mavlm_pool_bilinear": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "mavlm_attention_bwd": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32,

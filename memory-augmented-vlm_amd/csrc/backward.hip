@@ -327,7 +327,7 @@ hipError_t launch_ln_bwd(const uint16_t* dy, const float* x, const uint16_t* res
   do {                                                                                                              \
     static mavlm_per_device_once once;                                                                              \
     if (lds > 65536) {                                                                                              \
-      hipError_t ae = once.dyn_lds((const void*)layernorm_bwd_kernel<T, NV>, 3 * 2 * 4096 * 4);                     \
+      hipError_t ae = once.dyn_lds((const void*)layernorm_bwd_kernel<T, NV>, 3 * 2 * MAVLM_LN_MAX_D * 4);           \
       if (ae != hipSuccess) return ae;                                                                              \
     }                                                                                                               \
     hipLaunchKernelGGL((layernorm_bwd_kernel<T, NV>), grid, block, lds, s, dy, x, res, ldr, gamma, dz, part, rows,   \
@@ -350,7 +350,7 @@ size_t mavlm_layernorm_bwd_partial_floats(int D) { return (size_t)(LNB_BLOCKS + 
 hipError_t mavlm_launch_layernorm_bwd(const void* dy, const float* x, const void* res, int ldr, const float* gamma,
                                       void* dz, float* dgamma, float* dbeta, float* part, int rows, int D, float eps,
                                       int dtype, hipStream_t s) {
-  if (rows <= 0 || (D & 3) || D > 4096) return hipErrorInvalidValue;
+  if (rows <= 0 || (D & 3) || D > MAVLM_LN_MAX_D) return hipErrorInvalidValue;
   mavlm_prof_scope prof(MAVLM_K_LN, 0.0, 12.0 * rows * (double)D, s);
   hipError_t e = dtype == MAVLM_F16
                      ? launch_ln_bwd<F16>((const uint16_t*)dy, x, (const uint16_t*)res, ldr, gamma, (uint16_t*)dz, part, rows, D, eps, s)

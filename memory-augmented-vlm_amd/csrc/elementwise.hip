@@ -403,27 +403,39 @@ void ln8_launch(const float* x, const void* res, int ldr, const float* g, const 
 template <typename T>
 hipError_t ln_dispatch(const float* x, const void* res, int ldr, const float* g, const float* b, void* out, int rows, int D,
                        float eps, hipStream_t s) {
-  if ((D & 7) == 0 && (ldr & 7) == 0 && D <= 4096) {       // 16-byte accesses to the 16-bit data
-    const int nc = (D / 8 + 63) / 64;
-    if (nc <= 1) ln8_launch<T, 1>(x, res, ldr, g, b, out, rows, D, eps, s);
-    else if (nc <= 2) ln8_launch<T, 2>(x, res, ldr, g, b, out, rows, D, eps, s);
-    else if (nc <= 4) ln8_launch<T, 4>(x, res, ldr, g, b, out, rows, D, eps, s);
-    else       // D > 2048: a workgroup per row (<= 2 chunks per lane; the wave-per-row form needs 246 VGPRs there: 1 wave per SIMD)
+  switch (mavlm_layernorm_form_of(D, ldr)) {               // the one place that picks the form (mirrored by mavlm_layernorm_form)
+    case MAVLM_LNF_LN8 + 1: ln8_launch<T, 1>(x, res, ldr, g, b, out, rows, D, eps, s); break;
+    case MAVLM_LNF_LN8 + 2: ln8_launch<T, 2>(x, res, ldr, g, b, out, rows, D, eps, s); break;
+    case MAVLM_LNF_LN8 + 4: ln8_launch<T, 4>(x, res, ldr, g, b, out, rows, D, eps, s); break;
+    case MAVLM_LNF_BLOCK:      // D > 2048: a workgroup per row (<= 2 chunks per lane; the wave-per-row form needs 246 VGPRs there: 1 wave per SIMD)
       hipLaunchKernelGGL((layernorm8_block_kernel<T, 2>), dim3(rows), dim3(256), 0, s, x, (const uint16_t*)res, ldr, g, b,
                          (uint16_t*)out, rows, D, eps);
-    return hipGetLastError();
+      break;
+    case MAVLM_LNF_FALLBACK + 1: ln_launch<T, 1>(x, res, ldr, g, b, out, rows, D, eps, s); break;
+    case MAVLM_LNF_FALLBACK + 2: ln_launch<T, 2>(x, res, ldr, g, b, out, rows, D, eps, s); break;
+    case MAVLM_LNF_FALLBACK + 4: ln_launch<T, 4>(x, res, ldr, g, b, out, rows, D, eps, s); break;
+    case MAVLM_LNF_FALLBACK + 8: ln_launch<T, 8>(x, res, ldr, g, b, out, rows, D, eps, s); break;
+    case MAVLM_LNF_FALLBACK + 16: ln_launch<T, 16>(x, res, ldr, g, b, out, rows, D, eps, s); break;
+    default: return hipErrorInvalidValue;
   }
-  const int nv = (D / 4 + 63) / 64;
-  if (nv <= 1) ln_launch<T, 1>(x, res, ldr, g, b, out, rows, D, eps, s);
-  else if (nv <= 2) ln_launch<T, 2>(x, res, ldr, g, b, out, rows, D, eps, s);
-  else if (nv <= 4) ln_launch<T, 4>(x, res, ldr, g, b, out, rows, D, eps, s);
-  else if (nv <= 8) ln_launch<T, 8>(x, res, ldr, g, b, out, rows, D, eps, s);
-  else if (nv <= 16) ln_launch<T, 16>(x, res, ldr, g, b, out, rows, D, eps, s);
-  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
 }  // namespace
+
+// The form mavlm_launch_layernorm runs for rows of D columns over a residual of row stride ldr (0: no residual): the 8-element
+// chunks (16-byte accesses to the 16-bit data) with 1 / 2 / 4 chunks per lane of a wave per row, a workgroup per row above 2048
+// columns, or the 4-element fallback (D % 8 == 4, or a residual stride that is no multiple of 8) with 1 .. 16 float4 per lane;
+// MAVLM_LNF_REFUSED: no kernel (D % 4, ldr % 4, more than MAVLM_LN_MAX_D columns).  Host only, a pure function of (D, ldr).
+int mavlm_layernorm_form_of(int D, int ldr) {
+  if (D <= 0 || (D & 3) || ldr < 0 || (ldr & 3) || D > MAVLM_LN_MAX_D) return MAVLM_LNF_REFUSED;
+  if ((D & 7) == 0 && (ldr & 7) == 0) {
+    const int nc = (D / 8 + 63) / 64;
+    return nc <= 1 ? MAVLM_LNF_LN8 + 1 : nc <= 2 ? MAVLM_LNF_LN8 + 2 : nc <= 4 ? MAVLM_LNF_LN8 + 4 : MAVLM_LNF_BLOCK;
+  }
+  const int nv = (D / 4 + 63) / 64;
+  return MAVLM_LNF_FALLBACK + (nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 8 ? 8 : 16);
+}
 
 hipError_t mavlm_launch_layernorm(const float* x, const void* res, int ldr, const float* gamma, const float* beta,
                                   void* out, int rows, int D, float eps, int dtype, hipStream_t s) {
@@ -438,7 +450,7 @@ hipError_t mavlm_launch_layernorm_planes(const float* planes, int splits, const 
                                          const float* gamma, const float* beta, void* out, int rows, int D, float eps, int dtype,
                                          hipStream_t s) {
   if (rows <= 0) return hipSuccess;
-  if (!planes || !gamma || !beta || !out || splits < 1 || D <= 0 || (D & 7) || D > 4096 || (res && (ldr & 7))) return hipErrorInvalidValue;
+  if (!planes || !gamma || !beta || !out || splits < 1 || D <= 0 || (D & 7) || D > MAVLM_LN_MAX_D || (res && (ldr & 7))) return hipErrorInvalidValue;
   mavlm_prof_scope prof(MAVLM_K_LN, 0.0, (res ? 4.0 : 2.0) * rows * (double)D + 4.0 * splits * rows * (double)D, s);
   const int nc = (D / 8 + 63) / 64;
 #define LNP(TT)                                                                                                              \

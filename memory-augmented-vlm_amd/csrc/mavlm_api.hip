@@ -96,9 +96,11 @@ inline int q_tokens(const mavlm_config& c) { return c.q_tokens > 0 ? c.q_tokens 
 inline int q_row0(const mavlm_config& c) { return c.q_tokens > 0 ? c.q_token0 * c.patches : 0; }
 
 // shapes the gfx950 kernels implement (DESIGN.md "Supported shapes"): head_dim <= 128 (heads are zero-padded to
-// 128 columns in the Q/K/V/ctx buffers and in the packed weights), D and I multiples of 128
+// 128 columns in the Q/K/V/ctx buffers and in the packed weights), D and I multiples of 128, D <= MAVLM_MAX_HIDDEN (the
+// widest row of the LayerNorm kernels, forward and backward: a wider context would fail inside its first step)
+static_assert(MAVLM_MAX_HIDDEN == MAVLM_LN_MAX_D, "include/mavlm.h and mavlm_kernels.h state the same limit");
 bool shape_ok(const mavlm_config* c) {
-  if (c->hidden % 128 != 0 || c->hidden % c->heads != 0 || c->inter % 128 != 0) return false;
+  if (c->hidden % 128 != 0 || c->hidden % c->heads != 0 || c->inter % 128 != 0 || c->hidden > MAVLM_MAX_HIDDEN) return false;
   const int hd = c->hidden / c->heads;
   return hd <= 128 || hd == 448;      // 448: wide-head kernels (attention_hd.hip), no padding
 }
@@ -412,7 +414,7 @@ int dense_ln(mavlm_ctx* x, hipStream_t s, const void* A, int lda, const void* W,
   }
   // small grids whose contraction is split (the 4D -> D projection at few memory tokens): the fp32 planes go straight into a
   // reduce + bias + residual + LayerNorm kernel - no reduction pass, no fp32 round trip of the dense output (same bits)
-  if (g_mavlm_splitk_ln && vw(x).gsplit_floats && (N & 7) == 0 && N <= 4096 &&
+  if (g_mavlm_splitk_ln && vw(x).gsplit_floats && (N & 7) == 0 && N <= MAVLM_LN_MAX_D &&
       mavlm_gemm_split_ws_floats(rows, N, K, MAVLM_EPI_F32, N) != 0 &&
       mavlm_gemm_split_ws_floats(rows, N, K, MAVLM_EPI_F32, N) <= vw(x).gsplit_floats) {
     mavlm_gemm_args g;
@@ -1796,6 +1798,8 @@ int mavlm_layernorm(const float* xin, const void* res, int32_t ldr, const float*
   hipError_t e = mavlm_launch_layernorm(xin, res, ldr, gamma, beta, out, rows, D, eps, dtype, (hipStream_t)stream);
   return e == hipErrorInvalidValue ? MAVLM_E_ARG : (int)e;
 }
+
+int mavlm_layernorm_form(int32_t D, int32_t ldr) { return mavlm_layernorm_form_of(D, ldr); }
 
 int mavlm_pool_bilinear(const void* xin, void* out, const void* pe_table, const int64_t* idx, int32_t F, int32_t side,
                         int32_t stride, int32_t D, int32_t dtype, void* stream) {

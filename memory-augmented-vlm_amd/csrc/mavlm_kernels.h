@@ -280,6 +280,13 @@ hipError_t mavlm_launch_frame_scores(const float* part, int planes, int H, int S
 // biased variance; rsqrt(var+eps))
 hipError_t mavlm_launch_layernorm(const float* x, const void* res, int ldr, const float* gamma, const float* beta,
                                   void* out, int rows, int D, float eps, int dtype, hipStream_t s);
+// widest row of the LayerNorm kernels, forward and backward (16 float4 per lane of a wave; the backward's 96 KiB of LDS), and
+// so the widest hidden size a context is created for (include/mavlm.h MAVLM_MAX_HIDDEN)
+constexpr int MAVLM_LN_MAX_D = 4096;
+// the form mavlm_launch_layernorm takes (elementwise.hip; include/mavlm.h mavlm_layernorm_form): MAVLM_LNF_LN8 + chunks per lane
+// (1 / 2 / 4), MAVLM_LNF_BLOCK, MAVLM_LNF_FALLBACK + float4 per lane (1 / 2 / 4 / 8 / 16), MAVLM_LNF_REFUSED
+enum { MAVLM_LNF_REFUSED = 0, MAVLM_LNF_LN8 = 100, MAVLM_LNF_BLOCK = 200, MAVLM_LNF_FALLBACK = 300 };
+int mavlm_layernorm_form_of(int D, int ldr);
 // the same with x given as `splits` fp32 planes of a split-K GEMM ([splits][rows][D], summed in order) + bias [D]: the reduction pass
 // and the LayerNorm in one kernel (same arithmetic as mavlm_launch_splitk_reduce followed by mavlm_launch_layernorm: same bits).
 // D % 8 == 0, D <= 4096, ldr % 8 == 0

@@ -103,6 +103,25 @@ def floor_gate(name, got, ref, rows, cols, floor, unit, whole_max=None):
     return Gate(name, float(ratio.view(-1)[i]), divmod(i, ratio.shape[1]), whole, gf, unit, whole_max)
 
 
+def layernorm_ref64(x, res, gamma, beta, eps):
+    """LayerNorm(x + res) * gamma + beta in float64 (biased variance, two passes): x fp32 [rows, D], res 16-bit [rows, D] or
+    None, gamma / beta [D]; tensors of any device or numpy arrays."""
+    z = f64(x) + (f64(res) if res is not None else 0.0)
+    mu = z.mean(dim=1, keepdim=True)
+    var = (z - mu).square().mean(dim=1, keepdim=True)
+    return (z - mu) / torch.sqrt(var + eps) * f64(gamma) + f64(beta)
+
+
+LN_ROWS = 4     # rows of a LayerNorm gate block: the rows of one workgroup of the wave-per-row forms (csrc/elementwise.hip)
+
+
+def layernorm_gate(name, out, ref, mode):
+    """Row LayerNorm forward: `out` within BWD_BLOCK x floor per block of LN_ROWS rows, the floor being the float64 `ref` rounded
+    once to the output grid (the kernels compute in fp32 and round once: the expected ratio is 1.0)."""
+    ref = f64(ref)
+    return floor_gate(name, out, ref, LN_ROWS, ref.shape[1], mode, BWD_BLOCK)
+
+
 def attention_gate(ctx, lse2, ref_ctx, ref_lse2, heads, mode):
     """Forward attention: ctx within ATTN_UNIT x floor per (128-query unit, head) and ATTN_WHOLE x floor over the tensor; lse2
     (log2 domain, [H, R]) within LSE2_ATOL of the reference on every row.  Returns (gate, worst lse2 error, passed)."""

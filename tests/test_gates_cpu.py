@@ -2,14 +2,16 @@
 accept a correctly rounded result.  Reduced shapes, numpy float64 references; the "kernel outputs" are that reference with one
 realistic defect planted: a stream-K unit that drops one of its 16 key pieces, one unit whose merge weight is off by 2^-6, one
 row's log-sum-exp off by 2e-4, one GEMM tile whose contraction stops short, a dK missing one 64-row query tile's contribution
-(the backward gate of test_gpu_backward_m64.py), a dW whose last split-K range is dropped or counted twice."""
+(the backward gate of test_gpu_backward_m64.py), a dW whose last split-K range is dropped or counted twice, LayerNorm rows whose
+statistics miss a chunk of 8 elements (the gate of test_gpu_layernorm_forms.py)."""
 import math
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import memory_path as O
-from gpu_util import BWD_BLOCK, attention_bwd_ref64, attention_gate, floor_gate, gemm_gate
+from gpu_util import BWD_BLOCK, attention_bwd_ref64, attention_gate, floor_gate, gemm_gate, layernorm_gate, layernorm_ref64, round_to
 
 R, S, H, HD = 8192, 512, 2, 64         # 64 128-query units per head; a unit's keys in 16 pieces of 32
 PIECES = 16
@@ -128,3 +130,55 @@ def test_tile_gate_rejects_a_dw_with_its_last_split_wrong():
         one = ref.copy()
         one[256:, :256] = bad[256:, :256]                   # in one 256 x 256 tile only
         assert not gemm_gate(O.bf16_round(one.astype(np.float32)), ref, "bf16")[1]
+
+
+def _layernorm_defects(x, res, g, b, eps):
+    """float64 outputs of three wrong kernels on rows z = x + res: the mean taken over D - 8 elements (a dropped chunk), the
+    last 8 residual elements not added, the variance divided by D + 8; and `dropped sum`: the chunk missing from the sum only
+    (mean = sum over D - 8 elements / D), what dropping a chunk from the kernels' first pass gives."""
+    d = x.shape[1]
+    z = x.astype(np.float64) + res
+    ln = lambda zz, mean, var: torch.from_numpy((zz - mean) / np.sqrt(var + eps) * g + b)
+    mu, var = z.mean(1, keepdims=True), z.var(1, keepdims=True)
+    nr = z.copy()
+    nr[:, -8:] = x[:, -8:]
+    return {"mean over D - 8": ln(z, z[:, :-8].mean(1, keepdims=True), var),
+            "last 8 residual elements missing": ln(nr, nr.mean(1, keepdims=True), nr.var(1, keepdims=True)),
+            "variance / (D + 8)": ln(z, mu, var * d / (d + 8)),
+            "dropped sum": ln(z, z[:, :-8].sum(1, keepdims=True) / d, var)}
+
+
+@pytest.mark.parametrize("mode", ["bf16", "fp16"])
+def test_layernorm_gate_rejects_rows_with_wrong_statistics(mode):
+    """The gate of tests/test_gpu_layernorm_forms.py (per block of 4 rows, BWD_BLOCK x the floor of float64 rounded once to the
+    output grid) on the rows of that test: x = 3 N(0,1) + 0.5 and x = 64 + N(0,1), a 16-bit residual.  The rounded float64
+    result passes at a ratio of exactly 1; the outputs of `_layernorm_defects` are rejected
+      - with ONE row of 37 wrong (a quarter of its block) at D = 256 on the first kind of rows, and
+      - with every row wrong, as a kernel defect is, at D = 512 and 1024 on both kinds.
+    A defect in 8 of D elements of the statistics moves the output by ~8 / D, the floor is 2^-9 / 2^-12 whatever D: at D = 4096
+    the bf16 gate no longer sees a mean over D - 8 elements or a variance over D + 8 (1.1 - 1.2 x floor with every row wrong),
+    the fp16 gate does (4.3 x or more) - one reason the GPU test runs both types - and both see the missing residual elements
+    and, on the rows of 64 + N(0,1), the chunk dropped from the sum (the shift of the mean is 8 x 64 / D): asserted at 4096."""
+    rows, eps, bad_row = 37, 1e-12, 21
+    for d in (256, 512, 1024, 4096):
+        g = 1.0 + O.hash_uniform((d,), 52, -0.1, 0.1).astype(np.float64)
+        b = O.hash_uniform((d,), 53, -0.1, 0.1).astype(np.float64)
+        res = round_to(O.hash_normal_like((rows, d), 54), mode).numpy()
+        for kind, x in (("3 N + 0.5", O.hash_normal_like((rows, d), 51) * 3.0 + 0.5), ("64 + N", O.hash_normal_like((rows, d), 55) + 64.0)):
+            x = x.astype(np.float32)
+            ref = layernorm_ref64(x, res, g, b, eps)
+            good = layernorm_gate("rounded float64", round_to(ref, mode), ref, mode)
+            assert good.ok and good.worst == 1.0, str(good)
+            for name, out in _layernorm_defects(x, res, g, b, eps).items():
+                every = layernorm_gate(f"D {d} {kind}: {name}, every row", round_to(out, mode), ref, mode)
+                one = ref.clone()
+                one[bad_row] = out[bad_row]
+                single = layernorm_gate(f"D {d} {kind}: {name}, one row", round_to(one, mode), ref, mode)
+                print(every, single, sep="\n")
+                if d == 256 and kind == "3 N + 0.5":
+                    assert not single.ok and single.where == (bad_row // 4, 0), str(single)
+                if d in (512, 1024):
+                    assert not every.ok, str(every)
+                if d == 4096 and (mode == "fp16" or name == "last 8 residual elements missing" or
+                                  (name == "dropped sum" and kind == "64 + N")):
+                    assert not every.ok, str(every)

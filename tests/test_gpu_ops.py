@@ -502,14 +502,17 @@ def test_pool_bilinear_vs_oracle_and_reference_golden(mode):
 @pytest.mark.parametrize("mode", ["bf16", "fp16"])
 @pytest.mark.parametrize("hd,R,S,H", [(128, 200, 300, 2), (448, 16, 32, 1), (448, 200, 300, 2), (448, 129, 97, 1),
                                       (448, 392, 588, 8), (128, 1, 1, 1), (448, 1, 1, 1), (448, 196, 2048, 2),
-                                      (128, 100, 1100, 1), (448, 1568, 6272, 8)])
+                                      (128, 100, 1100, 1), (448, 1568, 6272, 8),
+                                      (224, 200, 300, 2), (256, 200, 300, 2), (224, 129, 97, 1), (256, 16, 32, 1),
+                                      (224, 1, 1, 1), (256, 1, 1, 1), (224, 196, 2048, 2), (256, 100, 1100, 1)])
 @pytest.mark.parametrize("groups", [2, 1])
 def test_attention_wide_heads_vs_oracle(mode, hd, R, S, H, groups):
     """attention_hd.hip: head_dim 448 (LLaVA-OneVision-7B) with the pipelined 32-query waves (groups = 2, the default) and
     with the 16-query waves of rounds 1-2 (groups = 1), and 128 (cross-check of the same machinery); oracle emulation with
     32-key tiles and the deferred-rescale decision per 16 / 32 query rows.  The last three
-    shapes are small grids with many key tiles: the kernel splits the keys (partials + merge), the oracle mirrors the
-    plan."""
+    shapes of 128 / 448 are small grids with many key tiles: the kernel splits the keys (partials + merge), the oracle mirrors
+    the plan.  head_dim 224 / 256 (the four heads of the TransformerEncoder Memory-Fuser at hidden 896 / 1024): the same
+    shapes, the last two split; no column-sum kernel exists at these two head sizes, so that part runs at 128 / 448 only."""
     if hd != 448 and groups == 1:
         pytest.skip("one kernel form below 448")
     capi.lib().mavlm_set_attention_wide_groups(groups)
@@ -530,6 +533,8 @@ def _wide_heads_vs_oracle(mode, hd, R, S, H, wave_rows):
                              wide_kernel=True)
     assert O.rel_l2(to_np(got), r(ctx)) < TOL
     np.testing.assert_allclose(to_np(lse), lse2, rtol=0, atol=3e-3)
+    if hd not in (128, 448):
+        return
     part = ops.attention_colsum(to_dev(q, mode), to_dev(k, mode), lse, H, head_dim=hd, wide_kernel=True)
     assert O.rel_l2(to_np(part), col) < TOL
     assert abs(float(part.sum()) - H * R) < 1e-3 * H * R
@@ -592,15 +597,22 @@ def test_attention_wide_heads_identity_v_and_rescale(groups):
         capi.lib().mavlm_set_attention_wide_groups(0)
 
 
-def _wide_identity_v(groups):
-    R, S, H, hd = 48, 160, 1, 448
+@pytest.mark.parametrize("hd", [224, 256])
+def test_attention_wide_heads_identity_v_and_rescale_224_256(hd):
+    """The same at the head sizes of the TransformerEncoder Memory-Fuser: at 224 the second 128-column sub-image of a head is
+    partly padding (96 of 128 columns), at 256 it is full."""
+    _wide_identity_v(2, hd)
+
+
+def _wide_identity_v(groups, hd=448):
+    R, S, H = 48, 160, 1
     r = O.bf16_round
     q = r(O.hash_normal_like((R, hd), 91) * 0.3)
     k = r(O.hash_normal_like((S, hd), 92) * 0.3)
     v = np.zeros((S, hd), np.float32)
     v[np.arange(S), (np.arange(S) * 11 + 5) % hd] = 1.0
     k[32 * 4 + 17] = r(q[5] * 6.0)
-    ctx, lse2, _, _ = O.attention_heads(q, k, v, H, "bf16", kv_tile=32, wave_rows=32 if groups == 2 else 16)
+    ctx, lse2, _, _ = O.attention_heads(q, k, v, H, "bf16", kv_tile=32, wave_rows=32 if (groups == 2 and hd == 448) else 16)
     got, lse = ops.attention(to_dev(q), to_dev(k), to_dev(v), H, want_lse=True, head_dim=hd)
     assert O.rel_l2(to_np(got), r(ctx)) < TOL
     np.testing.assert_allclose(to_np(lse), lse2, rtol=0, atol=5e-3)

@@ -70,10 +70,13 @@ def make_projector(cfg: O.PathConfig, w, mode="bf16", cache_cap=10):
 @pytest.mark.parametrize("mode,H,M,frames,hd", [("bf16", 8, 8, [3, 2, 3, 1], 128), ("fp16", 2, 4, [2, 1, 2], 128),
                                                  ("bf16", 1, 3, [1, 1], 128), ("bf16", 8, 8, [2, 3, 1], 112),
                                                  ("fp16", 4, 2, [1, 2], 64), ("bf16", 2, 4, [2, 1, 2], 448),
-                                                 ("bf16", 8, 8, [2, 1], 448)])
+                                                 ("bf16", 8, 8, [2, 1], 448), ("bf16", 12, 2, [2, 1], 128),
+                                                 ("fp16", 16, 1, [1, 2], 128), ("bf16", 12, 2, [2, 1], 96)])
 def test_recurrent_steps_vs_oracle(mode, H, M, frames, hd):
     """hd = 112 is the Qwen2-0.5B shape (D = 896, the reference Config default): heads run zero-padded to 128.
-    hd = 448 is the LLaVA-OneVision-7B shape (D = 3584 with 8 heads): wide-head kernels, attention_hd.hip."""
+    hd = 448 is the LLaVA-OneVision-7B shape (D = 3584 with 8 heads): wide-head kernels, attention_hd.hip.
+    The last three are narrow heads above hidden 1024 (1536, 2048, 1152): `layernorm8_kernel<T, 4>` and its split-K form in a
+    real step, 12 heads, and with 12 heads of 96 a padded width (1536) that differs from hidden (1152) at N % 256 == 128."""
     cfg = O.PathConfig(hidden=hd * H, heads=H, mem_tokens=M, depth=2)
     w = O.make_weights(cfg, seed=5, grid=mode)
     proj = make_projector(cfg, w, mode)
@@ -416,12 +419,16 @@ def test_frame_scores_from_tile_entries_on_small_grids(M, frames):
             assert O.rel_l2(to_np(s2), to_np(s0)) < 5e-3
 
 
-@pytest.mark.parametrize("hidden,hd", [(1024, 128), (3584, 448)])
-def test_splitk_reduction_inside_the_layernorm_kernel_same_bits(hidden, hd):
+@pytest.mark.parametrize("hidden,heads,M", [pytest.param(1024, 8, 8, id="1024-128"), pytest.param(3584, 8, 8, id="3584-448"),
+                                            pytest.param(1536, 12, 4, id="1536-128"), pytest.param(2048, 16, 2, id="2048-128")])
+def test_splitk_reduction_inside_the_layernorm_kernel_same_bits(hidden, heads, M):
     """Round 4: where the 4D -> D projection splits its contraction (few memory tokens), the fp32 planes go straight into one reduce
     + bias + residual + LayerNorm kernel (`mavlm_launch_layernorm_planes`) instead of a reduction pass, an fp32 dense output and the
-    LayerNorm kernel (`mavlm_set_splitk_layernorm(0)`): the same additions in the same order - memories and scores bit for bit."""
-    cfg = O.PathConfig(hidden=hidden, heads=8, mem_tokens=8, depth=2)
+    LayerNorm kernel (`mavlm_set_splitk_layernorm(0)`): the same additions in the same order - memories and scores bit for bit.
+    Hidden 1024 / 3584 reach `layernorm8_kernel<T, 2, SK>` and the block form, 1536 / 2048 `layernorm8_kernel<T, 4, SK>` (at fewer
+    memory tokens: with 8 these widths no longer split); every shape is asserted to split, so the two runs are never one path."""
+    cfg = O.PathConfig(hidden=hidden, heads=heads, mem_tokens=M, depth=2)
+    assert capi.lib().mavlm_linear_ws_floats(M * 196, hidden, cfg.inter, capi.EPI_F32, hidden) > 0
     w = O.make_weights(cfg, seed=79)
     proj = make_projector(cfg, w)
     segs = [to_dev(O.bf16_round(O.hash_normal_like((F, 196, hidden), 7900 + t))) for t, F in enumerate((32, 7, 2))]
@@ -817,13 +824,18 @@ def test_config3_shape_long_video_ov7b_hipgraph():
     assert torch.equal(out, eager)
 
 
-@pytest.mark.parametrize("depth,cap,H,hd,M,frames", [(1, 10, 8, 128, 8, [2, 1, 2]), (3, 1, 4, 128, 2, [1, 2, 1]),
-                                                     (2, 2, 16, 64, 3, [1, 1, 1, 1]), (4, 10, 1, 128, 1, [1, 2])])
-def test_config_corners_vs_oracle(depth, cap, H, hd, M, frames):
+@pytest.mark.parametrize("depth,cap,H,hd,M,frames,inter", [(1, 10, 8, 128, 8, [2, 1, 2], None), (3, 1, 4, 128, 2, [1, 2, 1], None),
+                                                           (2, 2, 16, 64, 3, [1, 1, 1, 1], None), (4, 10, 1, 128, 1, [1, 2], None),
+                                                           (2, 10, 32, 128, 1, [1, 1], 4096)],
+                         ids=["1-10-8-128-8-frames0", "3-1-4-128-2-frames1", "2-2-16-64-3-frames2", "4-10-1-128-1-frames3",
+                              "widest-4096-32heads"])
+def test_config_corners_vs_oracle(depth, cap, H, hd, M, frames, inter):
     """Corners of the configuration space: depth 1 (the reference Config default) up to the ABI maximum, a FIFO of one
-    entry (every step evicts), 16 narrow heads, a single memory token; inference and training forward, bit-identical
-    to each other and inside the chain tolerance of the oracle."""
-    cfg = O.PathConfig(hidden=H * hd, heads=H, mem_tokens=M, depth=depth, cache_cap=cap)
+    entry (every step evicts), 16 narrow heads, a single memory token, the widest admitted hidden size (4096 = 32 heads of 128,
+    MAVLM_MAX_HIDDEN: the LayerNorm block form and the backward's 96 KiB of LDS in a real step; a small intermediate size
+    keeps the oracle to seconds); inference and training forward, bit-identical to each other and inside the chain tolerance
+    of the oracle."""
+    cfg = O.PathConfig(hidden=H * hd, heads=H, mem_tokens=M, depth=depth, cache_cap=cap, inter=inter)
     w = O.make_weights(cfg, seed=40 + depth)
     proj = make_projector(cfg, w, "bf16", cache_cap=cap)
     segs = [O.bf16_round(O.hash_normal_like((f, 196, cfg.hidden), 4000 + t)) for t, f in enumerate(frames)]
@@ -834,6 +846,8 @@ def test_config_corners_vs_oracle(depth, cap, H, hd, M, frames):
         cache, scores = proj(to_dev(s_))
         assert len(cache) == min(t + 1, cap)
         floor = O.rel_l2(alt[t][0][-1], ref[t][0][-1])
+        print(f"hidden {cfg.hidden} H={H} depth {depth} step {t}: HIP vs oracle {O.rel_l2(to_np(cache[-1]), ref[t][0][-1]):.2e}, "
+              f"oracle f64-acc vs f32-acc (floor) {floor:.2e}")
         assert O.rel_l2(to_np(cache[-1]), ref[t][0][-1]) < chain_tol(floor)
         assert O.rel_l2(to_np(scores[-1]), ref[t][1]) < max(5e-3, 4 * O.rel_l2(alt[t][1], ref[t][1]))
     infer = [c.clone() for c in cache]

@@ -44,8 +44,8 @@ import streamk_cases as T
 pytestmark = pytest.mark.gpu
 TOL = 1e-3                       # the gate of the existing frame-score tests (test_gpu_ops.py, test_gpu_batch.py, test_gpu_frames_lds.py)
 LOG2E = 1.4426950408889634
-UNDER = {128: 16.0, 448: 8.0}    # scale of the `under` row: lse2 = scale |q_h|^2 / sqrt(hd) log2 e ...
-UNDER_NORM2 = {128: 100.0, 448: 400.0}   # ... ~ 204 / 218 for the row of a unit with |q_h|^2 nearest to this (mean: hd)
+UNDER = {128: 16.0, 448: 8.0, 224: 8.0, 256: 8.0}    # scale of the `under` row: lse2 = scale |q_h|^2 / sqrt(hd) log2 e ...
+UNDER_NORM2 = {128: 100.0, 448: 400.0, 224: 240.0, 256: 270.0}   # ... ~ 204 / 218 (185 / 195 at 224 / 256: tests/test_gpu_wide_heads_224_256.py) for the row of a unit with |q_h|^2 nearest to this (mean: hd)
 
 
 @pytest.fixture(autouse=True)
@@ -65,7 +65,7 @@ def _hooks(request, monkeypatch):
 
 def _geom(kernel):
     """(head_dim, queries per unit, keys per tile)"""
-    return {"w8": (128, 256, 64), "w4": (128, 128, 64), "wide": (448, 128, 32)}[kernel]
+    return {"w8": (128, 256, 64), "w4": (128, 128, 64), "wide": (448, 128, 32), "wide224": (224, 128, 32), "wide256": (256, 128, 32)}[kernel]
 
 
 def _randn(shape, seed, mode):

@@ -23,9 +23,11 @@ def _module(D, w, mode):
     return m.cuda().to(DT[mode])
 
 
-@pytest.mark.parametrize("mode,D,N", [("bf16", 1024, 300), ("bf16", 896, 70), ("fp16", 512, 150), ("bf16", 512, 1)])
+@pytest.mark.parametrize("mode,D,N", [("bf16", 1024, 300), ("bf16", 896, 70), ("fp16", 512, 150), ("bf16", 512, 1),
+                                      ("bf16", 896, 1100), ("fp16", 1024, 1000)])
 def test_transformer_fuser_variant(mode, D, N):
-    """head_dim 256 / 224 / 128 on attention_hd.hip.  Gates: every layer teacher-forced on the oracle's input
+    """head_dim 256 / 224 / 128 on attention_hd.hip; the last two inputs are past the split-KV threshold of 993 tokens (key
+    planes + attn_combine_kernel; each head size on its own: tests/test_gpu_wide_heads_224_256.py).  Gates: every layer teacher-forced on the oracle's input
     <= 1e-3; the whole module against the oracle with a tolerance calibrated by the oracle's own fp32-vs-fp64
     accumulation distance (the chain decorrelates in 16-bit storage)."""
     w = V.fuser_weights(D, seed=7, grid=mode)

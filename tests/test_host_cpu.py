@@ -63,7 +63,19 @@ def test_config_validation_without_gpu(built_lib):
     bad = capi.Config(hidden=2048, heads=8, patches=196, mem_tokens=8, depth=2, inter=8192, cache_cap=10,
                       max_chunk_frames=32, dtype=0, eps=1e-12)               # head_dim 256: no kernel for it
     assert lib.mavlm_create(bad, capi.vp()) == capi.E_SHAPE
-    bad2 = capi.Config(hidden=1024, heads=8, patches=196, mem_tokens=0, depth=2, inter=4096, cache_cap=10,
+    # the widest hidden size is the widest row of the LayerNorm kernels (MAVLM_MAX_HIDDEN = 4096): refused at creation, where
+    # a wider context used to get a workspace and fail inside its first step
+    widest = capi.Config(hidden=4096, heads=32, patches=196, mem_tokens=8, depth=2, inter=4096, cache_cap=10,
+                         max_chunk_frames=32, dtype=0, eps=1e-12)
+    h4 = capi.vp()
+    assert lib.mavlm_create(widest, h4) == 0
+    lib.mavlm_destroy(h4)
+    for hidden, heads in ((4224, 33), (4480, 10)):                            # 33 heads of 128; 10 heads of 448
+        wider = capi.Config(hidden=hidden, heads=heads, patches=196, mem_tokens=8, depth=2, inter=4096, cache_cap=10,
+                            max_chunk_frames=32, dtype=0, eps=1e-12)
+        assert lib.mavlm_create(wider, capi.vp()) == capi.E_SHAPE, (hidden, heads)
+    assert lib.mavlm_layernorm_form(4096, 4096) == 200 and lib.mavlm_layernorm_form(4224, 4224) == 0
+    bad2 =capi.Config(hidden=1024, heads=8, patches=196, mem_tokens=0, depth=2, inter=4096, cache_cap=10,
                        max_chunk_frames=32, dtype=0, eps=1e-12)
     assert lib.mavlm_create(bad2, capi.vp()) == capi.E_ARG
     assert lib.mavlm_workspace_bytes(bad2) == 0
