@@ -21,6 +21,7 @@ backbone ops, restated in torch); a list without a video fails as the reference'
 beside the video are dropped as the reference drops them.  The anyres / multi-patch merge modes (:630-697) are unreachable
 in the reference's memory branch (its feature list only ever holds the memory and the fine frames) and are not restated.
 """
+import ctypes
 import math
 import random
 from typing import List, Optional
@@ -267,37 +268,192 @@ def video_memory_tokens(model, image: torch.Tensor, frame_idx_cpu: torch.Tensor,
     mp = memory_prompt_embeds.to(image.dtype).contiguous()
     fp = frame_prompt_embeds.to(image.dtype).contiguous()
     nl, nl_ptr = _newline_ptr(image_newline, layout, image.device, image.dtype)
-    import ctypes
     written = ctypes.c_int64(0)
     capi.check(capi.lib().mavlm_fuse_emit_layout(eng.ctx, x.data_ptr(), _device_indices(fine_cpu, image.device).data_ptr(), n_fine,
                                                  mp.data_ptr(), mp.shape[0], fp.data_ptr(), fp.shape[0], nl_ptr,
                                                  1 if with_frames else 0, capi.LAYOUTS[layout], out.data_ptr(), rows,
                                                  ctypes.byref(written), ops.stream_ptr()), "mavlm_fuse_emit_layout")
     assert written.value == rows
-    # memory_rows: the memory block with the newlines INSIDE it ("frame" / "grid"), without the one behind it ("one_token")
-    info = {"num_memories": n, "pe_frames": x, "fine_idx": fine_cpu,
-            "memory_rows": (mp.shape[0], mp.shape[0] + (mem_rows if layout_period(layout, P) else n * R))}
-    return out, info
+    return out, {"num_memories": n, "pe_frames": x, "fine_idx": fine_cpu, "memory_rows": _memory_rows(mp.shape[0], n, R, layout, P)}
 
 
-def _batch_pe_frames(pe, images, frame_idx_cpu, T):
-    """PE-added frames of the videos of a row batch (llava_arch.py:510-511).  `frame_idx_cpu`: one index tensor shared by the
-    videos, or a list of one per video, all of length T (two videos of 130 and 150 input frames both sample 128 frames, at
-    other original indices): the gather runs per video either way."""
+def _memory_rows(mp_rows, n, R, layout, P):
+    """`info["memory_rows"]`: the rows of the memory block inside a token block - with the newlines INSIDE it ("frame" / "grid"),
+    without the one behind it ("one_token")"""
+    return mp_rows, mp_rows + (layout_block_rows(n * R, layout, P) if layout_period(layout, P) else n * R)
+
+
+def _prepare_row_batch(kind, name, model, bp, images, frame_idx_cpu, chunk, fine_frames):
+    """What every row-batch driver does before the first step.  `kind`: "equal" (bp.batch videos of one length), "ragged"
+    (2 .. bp.batch videos, each a positive multiple of `chunk` frames, the same number of fine frames) or "clips" (2 .. bp.batch
+    videos of 1 .. chunk - 1 frames); `name`: the public function the caller called, for the error texts.  Validates the images
+    (GPU, [T_b, P, D], one dtype and device, the length rule of the kind) and `frame_idx_cpu` (one index tensor per video, of its
+    length; for "equal" also one tensor shared by all: two videos of 130 and 150 input frames both sample 128 frames, at other
+    original indices), orders the videos longest first (stable: the caller's order for equal lengths), adds the positional
+    encoding per video (llava_arch.py:510-511; consecutive videos with the same index tensor share its check and device copy)
+    and computes the fine-frame indices (:513-522).  Returns (xs, fines, order, back) - PE-added frames and fine indices in the
+    stepping order, `order[j]` = the caller's position of the j-th video stepped, `back` its inverse."""
+    k = len(images)
+    if (k != bp.batch) if kind == "equal" else (not 2 <= k <= bp.batch):
+        raise capi.MavlmError(f"{name}: {bp.batch if kind == 'equal' else f'2..{bp.batch}'} videos expected")
+    P, D = images[0].shape[1:]
+    dev, dt = images[0].device, images[0].dtype
+    for im in images:
+        if not im.is_cuda or im.dim() != 3 or tuple(im.shape[1:]) != (P, D) or im.dtype != dt or im.device != dev:
+            raise capi.MavlmError(f"{name}: GPU frame tokens [T_b, P, D] of one dtype / device expected")
+        T = im.shape[0]
+        if kind == "equal" and T != images[0].shape[0]:
+            raise capi.MavlmError(f"{name}: GPU frame tokens of one shape / dtype expected (videos of different lengths: "
+                                  "`ragged=True`, `video_memory_tokens_clips`, `video_memory_tokens_ragged_train`)")
+        if kind == "ragged" and (T < chunk or T % chunk):
+            raise capi.MavlmError(f"{name}: every video length must be a positive multiple of the chunk ({chunk} frames); got {T}")
+        if kind == "clips" and not 1 <= T < chunk:
+            raise capi.MavlmError(f"{name}: a clip has 1..{chunk - 1} frames (one chunk of all its frames); got {T}")
     if isinstance(frame_idx_cpu, (list, tuple)):
-        if len(frame_idx_cpu) != len(images) or any(i.numel() != T for i in frame_idx_cpu):
-            raise capi.MavlmError(f"row batch: one frame index tensor of {T} entries per video expected")
         idxs = list(frame_idx_cpu)
     else:
-        idxs = [frame_idx_cpu] * len(images)
-    dev = images[0].device
-    xs, last, last_dev = [], None, None
-    for im, idx in zip(images, idxs):
-        if idx is not last:
-            pe.check_indices(idx)
-            last, last_dev = idx, _device_indices(idx, dev)
-        xs.append(pe(im, last_dev, indices_checked=True))
-    return xs
+        idxs = [frame_idx_cpu] * k if kind == "equal" else []
+    if len(idxs) != k or any(i.numel() != im.shape[0] for i, im in zip(idxs, images)):
+        raise capi.MavlmError(f"{name}: one frame index tensor per video, of its length")
+    if kind == "clips" and D % 256:                  # (refused before any step: mavlm_fuse_emit_layout_frames_to would, afterwards)
+        raise capi.MavlmError(f"{name}: the clip emit needs a hidden size that is a multiple of 256; got {D}")
+    pe: TemporalPositionalEncoding = model.positional_encoding
+    order = sorted(range(k), key=lambda i: -images[i].shape[0])            # longest first; stable in the caller's order
+    back = [0] * k                                   # caller's position -> position in the stepping order
+    for j, i in enumerate(order):
+        back[i] = j
+    xs, fines, fine_of, last, last_dev = [], [], {}, None, None
+    for i in order:
+        if idxs[i] is not last:
+            pe.check_indices(idxs[i])
+            last, last_dev = idxs[i], _device_indices(idxs[i], dev)
+        xs.append(pe(images[i], last_dev, indices_checked=True))                                    # :510-511
+        T = images[i].shape[0]
+        if T not in fine_of:
+            fine_of[T] = fine_frame_indices(T, fine_frames)                                         # :513-522
+        fines.append(fine_of[T])
+    if kind == "ragged" and any(f.numel() != fines[0].numel() for f in fines):
+        raise capi.MavlmError(f"{name}: the videos must have the same number of fine frames")
+    return xs, fines, order, back
+
+
+def _step_chunks(step, xs, chunk, ragged):
+    """Hands the videos' chunks (llava_arch.py:528,534-537) to `step` (`bp.step` / `bp.step_train`).  Equal lengths: every video's
+    chunk i, the last one shorter where the length is no multiple of `chunk`.  `ragged` (`xs` longest first, lengths multiples
+    of `chunk`): step i takes chunk i of the videos that still have one - a prefix that only shrinks."""
+    if ragged:
+        chunks = [x.shape[0] // chunk for x in xs]
+        for i in range(chunks[0]):
+            step([x[i * chunk:(i + 1) * chunk] for x, c in zip(xs, chunks) if c > i])
+        return
+    bounds = uniform_segment_variant(xs[0].shape[0], chunk)
+    for i in range(len(bounds) - 1):
+        step([x[bounds[i]:bounds[i + 1]] for x in xs])
+
+
+def _block_destination(name, out, dst_rows, rows, order, stacked, D, dev, dt):
+    """Where the emit writes the blocks (`rows[j]` rows for the j-th video stepped).  Returns (buffer, dst): with `dst_rows` the
+    caller's contiguous [out_rows, D] `out` and each video's first row in it; without, for `stacked` blocks (equal lengths) a
+    [k, rows, D] tensor - the caller's `out` or a new one - and None (constant stride), else ONE new [sum(rows), D] buffer and
+    the running offsets."""
+    k = len(rows)
+    if dst_rows is not None:
+        if out is None or out.dim() != 2 or out.shape[1] != D or out.dtype != dt or not out.is_contiguous() or not out.is_cuda \
+                or len(dst_rows) != k:
+            raise capi.MavlmError(f"{name}: `dst_rows` needs {k} rows of a contiguous [out_rows,{D}] {dt} GPU tensor `out`")
+        return out, [int(dst_rows[i]) for i in order]
+    if stacked:
+        if out is None:
+            out = torch.empty((k, rows[0], D), device=dev, dtype=dt)
+        elif tuple(out.shape) != (k, rows[0], D) or out.dtype != dt or not out.is_contiguous() or not out.is_cuda:
+            raise capi.MavlmError(f"{name}: `out` must be a contiguous [{k},{rows[0]},{D}] {dt} GPU tensor")
+        return out, None
+    if out is not None:
+        raise capi.MavlmError(f"{name}: `out` goes with `dst_rows` (the blocks differ in length)")
+    return torch.empty((sum(rows), D), device=dev, dtype=dt), [sum(rows[:j]) for j in range(k)]
+
+
+def _emit_row_batch(kind, eng, xs, fines, mp, fp, nl_ptr, with_frames, layout, buf, dst, rows):
+    """ONE emit for the blocks of every video of a row batch (fuser MLP + type adds + prompts / newlines, written in place).  The
+    export follows the kind of the batch and the destination - the equal-length and the ragged implementation group the fuser
+    GEMMs differently, so the choice is part of the result: mavlm_fuse_emit_layout_batch (equal lengths, stacked blocks) /
+    _batch_to (equal lengths, `dst`) / _ragged_to (per ring slot the fuser runs over the videos that hold it; a fine-frame
+    index row per video) / _frames_to (clips: a fine-frame count per video)."""
+    lib, k, dev = capi.lib(), len(xs), xs[0].device
+    xptrs = (capi.vp * k)(*[x.data_ptr() for x in xs])
+    tail = (mp.data_ptr(), mp.shape[0], fp.data_ptr(), fp.shape[0], nl_ptr, 1 if with_frames else 0, capi.LAYOUTS[layout])
+    if kind == "equal":
+        written = ctypes.c_int64(0)
+        fine = (_device_indices(fines[0], dev).data_ptr(), fines[0].numel())
+        if dst is None:
+            capi.check(lib.mavlm_fuse_emit_layout_batch(eng.ctx, xptrs, *fine, *tail, buf.data_ptr(), rows[0], ctypes.byref(written),
+                                                        ops.stream_ptr()), "mavlm_fuse_emit_layout_batch")
+        else:
+            capi.check(lib.mavlm_fuse_emit_layout_batch_to(eng.ctx, xptrs, *fine, *tail, buf.data_ptr(), buf.shape[0],
+                                                           (ctypes.c_int64 * k)(*dst), ctypes.byref(written), ops.stream_ptr()),
+                       "mavlm_fuse_emit_layout_batch_to")
+        assert written.value == rows[0]
+        return
+    written = (ctypes.c_int64 * k)()
+    where = (buf.data_ptr(), buf.shape[0], (ctypes.c_int64 * k)(*dst), written, ops.stream_ptr())
+    if kind == "ragged":
+        fine_dev = _device_indices(torch.cat(fines), dev)                        # [k, n_fine], one row per video
+        capi.check(lib.mavlm_fuse_emit_layout_ragged_to(eng.ctx, k, xptrs, fine_dev.data_ptr(), fines[0].numel(), *tail, *where),
+                   "mavlm_fuse_emit_layout_ragged_to")
+    else:
+        n_fines = [int(f.numel()) for f in fines]
+        fine_ld = max(n_fines) + (max(n_fines) & 1)                              # (even: every index row starts 16-byte aligned)
+        fine_cpu = torch.zeros((k, fine_ld), dtype=torch.long)
+        for j, f in enumerate(fines):
+            fine_cpu[j, :f.numel()] = f
+        fine_dev = _device_indices(fine_cpu.reshape(-1), dev)                    # [k, fine_ld], one row per video
+        capi.check(lib.mavlm_fuse_emit_layout_frames_to(eng.ctx, k, xptrs, fine_dev.data_ptr(), fine_ld, (capi.i32 * k)(*n_fines),
+                                                        *tail, *where), "mavlm_fuse_emit_layout_frames_to")
+    assert list(written) == rows
+
+
+def _row_batch_info(kind, bp, xs, fines, counts, rows, order, back, mp_rows, layout):
+    """`info` of a row-batch call.  "equal": one `num_memories`, `fine_idx`, `block_rows` for all videos and `memory_rows`;
+    otherwise `order` and per-video lists in the caller's order.  `counts`, `rows`: memories and block rows per video in the
+    stepping order (`rows` None: no `block_rows`)."""
+    if kind == "equal":
+        P = xs[0].shape[1]
+        info = {"num_memories": counts[0], "pe_frames": xs, "fine_idx": fines[0], "frame_scores": bp.frame_scores,
+                "memory_rows": _memory_rows(mp_rows, counts[0], bp.proj.num_memory_tokens * P, layout, P)}
+    else:
+        info = {"order": order, "num_memories": [counts[j] for j in back], "pe_frames": [xs[j] for j in back],
+                "fine_idx": [fines[j] for j in back], "frame_scores": bp.frame_scores}
+    if rows is not None:
+        info["block_rows"] = rows[0] if kind == "equal" else [rows[j] for j in back]
+    return info
+
+
+def _row_batch_tokens(kind, name, model, bp, images, frame_idx_cpu, memory_prompt_embeds, frame_prompt_embeds, image_newline,
+                      with_frames, chunk, fine_frames, out, layout, dst_rows):
+    """The inference driver of every row batch (`kind`, `name`: see _prepare_row_batch): prepare, `bp.reset()`, the steps, the
+    destination, one emit, `info`."""
+    layout_period(layout, images[0].shape[1])
+    xs, fines, order, back = _prepare_row_batch(kind, name, model, bp, images, frame_idx_cpu, chunk, fine_frames)
+    bp.reset()                                                                             # :532
+    if kind == "clips":
+        bp.step_frames(xs)                                                                 # :534-537: one chunk each
+    else:
+        _step_chunks(bp.step, xs, chunk, kind == "ragged")                                 # :534-537
+    P, D = xs[0].shape[1:]
+    dev, dt = xs[0].device, xs[0].dtype
+    eng = bp.engine(dev, dt)
+    M, cap, mp_rows = bp.proj.num_memory_tokens, eng.c.cache_cap, memory_prompt_embeds.shape[0]
+    rows = [video_token_rows(x.shape[0], M, P, with_frames, chunk, fine_frames, cap, mp_rows, frame_prompt_embeds.shape[0], layout)
+            for x in xs]
+    buf, dst = _block_destination(name, out, dst_rows, rows, order, kind == "equal", D, dev, dt)
+    mp = memory_prompt_embeds.to(dt).contiguous()
+    fp = frame_prompt_embeds.to(dt).contiguous()
+    nl, nl_ptr = _newline_ptr(image_newline, layout, dev, dt)
+    _emit_row_batch(kind, eng, xs, fines, mp, fp, nl_ptr, with_frames, layout, buf, dst, rows)
+    info = _row_batch_info(kind, bp, xs, fines, [min(-(-x.shape[0] // chunk), cap) for x in xs], rows, order, back, mp_rows, layout)
+    if kind == "equal" or dst_rows is not None:
+        return buf, info
+    return [buf[dst[j]:dst[j] + rows[j]] for j in back], info
 
 
 @torch.no_grad()
@@ -310,149 +466,20 @@ def video_memory_tokens_batched(model, bp: BatchedProjector, images, frame_idx_c
     weight-shared GEMM / LayerNorm of the path runs once over the stacked memory rows of all videos.  `images`: B tensors
     [T,196,D]; `frame_idx_cpu`: the original frame indices (shared: same length, same sampling).  Returns
     (tokens [B, rows, D] - video b's block is tokens[b] -, info).  Inference only.  `layout`: as video_memory_tokens.
-    `frame_idx_cpu` may be a list of B index tensors of one length (_batch_pe_frames).
+    `frame_idx_cpu` may be a list of B index tensors of one length.
     `dst_rows` (with `out` = a contiguous [out_rows, D] buffer, e.g. the padded inputs_embeds of a batch of samples seen as
     rows): video b's block is written at row dst_rows[b] of `out` (mavlm_fuse_emit_layout_batch_to: the same launches, one
     destination per video; rows outside the blocks are not touched); returns (out, info) with info["block_rows"].
-    `ragged=True`: 2 .. B videos whose lengths are multiples of `chunk` and may differ (`_video_memory_tokens_ragged`); returns
-    (list of [rows_b, D] blocks in the caller's order - or `out` with `dst_rows` -, info).  Without it unequal shapes are
+    `ragged=True`: k videos (2 <= k <= B) of T_b = c_b * `chunk` frames - lengths that may differ - on the one engine.  Internally
+    the videos are ordered by chunk count, longest first (stable); step i takes chunk i of the videos that still have one - a
+    prefix that only shrinks (`BatchedProjector.step`) -; ONE emit at the end writes every video's block
+    (`mavlm_fuse_emit_layout_ragged_to`).  `frame_idx_cpu`: one index tensor per video.  Returns (list of [rows_b, D] blocks in
+    the caller's order - or `out` with `dst_rows` -, info with `order` and per-video lists).  Without it unequal shapes are
     refused."""
-    layout_period(layout, images[0].shape[1])
-    if ragged:
-        return _video_memory_tokens_ragged(model, bp, images, frame_idx_cpu, memory_prompt_embeds, frame_prompt_embeds,
-                                           image_newline, with_frames, chunk, fine_frames, out, layout, dst_rows)
-    B = bp.batch
-    if len(images) != B:
-        raise capi.MavlmError(f"video_memory_tokens_batched: {B} videos expected")
-    T, P, D = images[0].shape
-    for im in images:
-        if not im.is_cuda or tuple(im.shape) != (T, P, D) or im.dtype != images[0].dtype:
-            raise capi.MavlmError("video_memory_tokens_batched: GPU frame tokens of one shape / dtype expected")
-    pe: TemporalPositionalEncoding = model.positional_encoding
-    rm: TransformerProjector = model.recurrent_memory_transformer
-    dev, dt = images[0].device, images[0].dtype
-    xs = _batch_pe_frames(pe, images, frame_idx_cpu, T)                                     # :510-511
-    fine_cpu = fine_frame_indices(T, fine_frames)                                          # :513-522
-    bounds = uniform_segment_variant(T, chunk)                                             # :528
-    bp.reset()                                                                             # :532
-    for i in range(len(bounds) - 1):                                                       # :534-537
-        bp.step([x[bounds[i]:bounds[i + 1]] for x in xs])
-    eng = bp.engine(dev, dt)
-    n = min(len(bounds) - 1, eng.c.cache_cap)
-    R = rm.num_memory_tokens * P
-    n_fine = fine_cpu.numel()
-    mem_rows = layout_block_rows(n * R, layout, P)
-    rows = memory_prompt_embeds.shape[0] + mem_rows
-    if with_frames:
-        rows += frame_prompt_embeds.shape[0] + layout_block_rows(n_fine * P, layout, P)
-    if dst_rows is not None:
-        if out is None or out.dim() != 2 or out.shape[1] != D or out.dtype != dt or not out.is_contiguous() or not out.is_cuda \
-                or len(dst_rows) != B:
-            raise capi.MavlmError(f"video_memory_tokens_batched: `dst_rows` needs {B} rows of a contiguous [out_rows,{D}] {dt} "
-                                  "GPU tensor `out`")
-    elif out is None:
-        out = torch.empty((B, rows, D), device=dev, dtype=dt)
-    elif tuple(out.shape) != (B, rows, D) or out.dtype != dt or not out.is_contiguous() or not out.is_cuda:
-        raise capi.MavlmError(f"video_memory_tokens_batched: `out` must be a contiguous [{B},{rows},{D}] {dt} GPU tensor")
-    mp = memory_prompt_embeds.to(dt).contiguous()
-    fp = frame_prompt_embeds.to(dt).contiguous()
-    nl, nl_ptr = _newline_ptr(image_newline, layout, dev, dt)
-    import ctypes
-    written = ctypes.c_int64(0)
-    xptrs = (capi.vp * B)(*[x.data_ptr() for x in xs])
-    info = {"num_memories": n, "pe_frames": xs, "fine_idx": fine_cpu, "block_rows": rows,
-            "memory_rows": (mp.shape[0], mp.shape[0] + (mem_rows if layout_period(layout, P) else n * R)),
-            "frame_scores": bp.frame_scores}
-    if dst_rows is not None:
-        dst = (ctypes.c_int64 * B)(*[int(r) for r in dst_rows])
-        capi.check(capi.lib().mavlm_fuse_emit_layout_batch_to(eng.ctx, xptrs, _device_indices(fine_cpu, dev).data_ptr(), n_fine,
-                                                              mp.data_ptr(), mp.shape[0], fp.data_ptr(), fp.shape[0], nl_ptr,
-                                                              1 if with_frames else 0, capi.LAYOUTS[layout], out.data_ptr(),
-                                                              out.shape[0], dst, ctypes.byref(written), ops.stream_ptr()),
-                   "mavlm_fuse_emit_layout_batch_to")
-        assert written.value == rows
-        return out, info
-    capi.check(capi.lib().mavlm_fuse_emit_layout_batch(eng.ctx, xptrs, _device_indices(fine_cpu, dev).data_ptr(), n_fine,
-                                                       mp.data_ptr(), mp.shape[0], fp.data_ptr(), fp.shape[0], nl_ptr,
-                                                       1 if with_frames else 0, capi.LAYOUTS[layout], out.data_ptr(), rows,
-                                                       ctypes.byref(written), ops.stream_ptr()), "mavlm_fuse_emit_layout_batch")
-    assert written.value == rows
-    return out, info
-
-
-def _video_memory_tokens_ragged(model, bp, images, frame_idx_cpu, memory_prompt_embeds, frame_prompt_embeds, image_newline,
-                                with_frames, chunk, fine_frames, out, layout, dst_rows):
-    """`video_memory_tokens_batched(ragged=True)`: k videos (2 <= k <= bp.batch) of T_b = c_b * `chunk` frames on one row-batched
-    engine.  Internally the videos are ordered by chunk count, longest first (stable); step i takes chunk i of the videos that
-    still have one - a prefix that only shrinks (`BatchedProjector.step`) -; ONE emit at the end writes every video's block
-    (`mavlm_fuse_emit_layout_ragged_to`: per ring slot the fuser runs over the videos that hold it; a fine-frame index row per
-    video).  The blocks come back in the caller's order."""
-    k = len(images)
-    if not 2 <= k <= bp.batch:
-        raise capi.MavlmError(f"video_memory_tokens_batched(ragged=True): 2..{bp.batch} videos expected")
-    P, D = images[0].shape[1:]
-    dev, dt = images[0].device, images[0].dtype
-    for im in images:
-        if not im.is_cuda or im.dim() != 3 or tuple(im.shape[1:]) != (P, D) or im.dtype != dt or im.device != dev:
-            raise capi.MavlmError("video_memory_tokens_batched: GPU frame tokens [T_b, P, D] of one dtype / device expected")
-        if im.shape[0] < chunk or im.shape[0] % chunk:
-            raise capi.MavlmError(f"video_memory_tokens_batched(ragged=True): every video length must be a positive multiple of "
-                                  f"the chunk ({chunk} frames); got {im.shape[0]}")
-    if not isinstance(frame_idx_cpu, (list, tuple)) or len(frame_idx_cpu) != k or \
-            any(i.numel() != im.shape[0] for i, im in zip(frame_idx_cpu, images)):
-        raise capi.MavlmError("video_memory_tokens_batched(ragged=True): one frame index tensor per video, of its length")
-    pe: TemporalPositionalEncoding = model.positional_encoding
-    rm: TransformerProjector = model.recurrent_memory_transformer
-    order = sorted(range(k), key=lambda i: -images[i].shape[0])            # longest first; stable in the caller's order
-    xs, fines = [], []
-    for i in order:
-        pe.check_indices(frame_idx_cpu[i])
-        xs.append(pe(images[i], _device_indices(frame_idx_cpu[i], dev), indices_checked=True))      # :510-511
-        fines.append(fine_frame_indices(images[i].shape[0], fine_frames))                           # :513-522
-    n_fine = fines[0].numel()
-    if any(f.numel() != n_fine for f in fines):
-        raise capi.MavlmError("video_memory_tokens_batched(ragged=True): the videos must have the same number of fine frames")
-    chunks = [x.shape[0] // chunk for x in xs]
-    bp.reset()                                                                                      # :532
-    for i in range(chunks[0]):                                                                      # :534-537, per video
-        bp.step([x[i * chunk:(i + 1) * chunk] for x, c in zip(xs, chunks) if c > i])
-    eng = bp.engine(dev, dt)
-    mp = memory_prompt_embeds.to(dt).contiguous()
-    fp = frame_prompt_embeds.to(dt).contiguous()
-    nl, nl_ptr = _newline_ptr(image_newline, layout, dev, dt)
-    R = rm.num_memory_tokens * P
-    rows = [video_token_rows(x.shape[0], rm.num_memory_tokens, P, with_frames, chunk, fine_frames, eng.c.cache_cap, mp.shape[0],
-                             fp.shape[0], layout) for x in xs]
-    if dst_rows is not None:
-        if out is None or out.dim() != 2 or out.shape[1] != D or out.dtype != dt or not out.is_contiguous() or not out.is_cuda \
-                or len(dst_rows) != k:
-            raise capi.MavlmError(f"video_memory_tokens_batched: `dst_rows` needs {k} rows of a contiguous [out_rows,{D}] {dt} "
-                                  "GPU tensor `out`")
-        buf, dst = out, [int(dst_rows[i]) for i in order]
-    else:
-        if out is not None:
-            raise capi.MavlmError("video_memory_tokens_batched(ragged=True): `out` goes with `dst_rows` (the blocks differ in length)")
-        buf = torch.empty((sum(rows), D), device=dev, dtype=dt)
-        dst = [sum(rows[:j]) for j in range(k)]
-    import ctypes
-    written = (ctypes.c_int64 * k)()
-    xptrs = (capi.vp * k)(*[x.data_ptr() for x in xs])
-    fine_dev = _device_indices(torch.cat(fines), dev)                        # [k, n_fine], one row per video
-    capi.check(capi.lib().mavlm_fuse_emit_layout_ragged_to(eng.ctx, k, xptrs, fine_dev.data_ptr(), n_fine, mp.data_ptr(), mp.shape[0],
-                                                           fp.data_ptr(), fp.shape[0], nl_ptr, 1 if with_frames else 0,
-                                                           capi.LAYOUTS[layout], buf.data_ptr(), buf.shape[0],
-                                                           (ctypes.c_int64 * k)(*dst), written, ops.stream_ptr()),
-               "mavlm_fuse_emit_layout_ragged_to")
-    assert list(written) == rows
-    back = [0] * k                               # caller's position -> position in the engine's order
-    for j, i in enumerate(order):
-        back[i] = j
-    info = {"order": order, "num_memories": [min(chunks[back[i]], eng.c.cache_cap) for i in range(k)],
-            "pe_frames": [xs[back[i]] for i in range(k)], "fine_idx": [fines[back[i]] for i in range(k)],
-            "block_rows": [rows[back[i]] for i in range(k)], "frame_scores": bp.frame_scores}
-    if dst_rows is not None:
-        return out, info
-    return [buf[dst[back[i]]:dst[back[i]] + rows[back[i]]] for i in range(k)], info
+    return _row_batch_tokens("ragged" if ragged else "equal",
+                             "video_memory_tokens_batched(ragged=True)" if ragged else "video_memory_tokens_batched", model, bp,
+                             images, frame_idx_cpu, memory_prompt_embeds, frame_prompt_embeds, image_newline, with_frames, chunk,
+                             fine_frames, out, layout, dst_rows)
 
 
 @torch.no_grad()
@@ -466,74 +493,8 @@ def video_memory_tokens_clips(model, bp: BatchedProjector, images, frame_idx_cpu
     (`mavlm_fuse_emit_layout_frames_to`; a clip's fine frames are all its frames, :513-522).  Internally the clips are ordered
     longest first (stable).  `images`: k tensors [T_b, P, D]; `frame_idx_cpu`: one index tensor per clip.  Returns (list of
     [rows_b, D] blocks in the caller's order - or `out`, a contiguous [out_rows, D] buffer, with `dst_rows` -, info).  Inference."""
-    layout_period(layout, images[0].shape[1])
-    k = len(images)
-    if not 2 <= k <= bp.batch:
-        raise capi.MavlmError(f"video_memory_tokens_clips: 2..{bp.batch} videos expected")
-    P, D = images[0].shape[1:]
-    dev, dt = images[0].device, images[0].dtype
-    for im in images:
-        if not im.is_cuda or im.dim() != 3 or tuple(im.shape[1:]) != (P, D) or im.dtype != dt or im.device != dev:
-            raise capi.MavlmError("video_memory_tokens_clips: GPU frame tokens [T_b, P, D] of one dtype / device expected")
-        if not 1 <= im.shape[0] < chunk:
-            raise capi.MavlmError(f"video_memory_tokens_clips: a clip has 1..{chunk - 1} frames (one chunk of all its frames); "
-                                  f"got {im.shape[0]}")
-    if not isinstance(frame_idx_cpu, (list, tuple)) or len(frame_idx_cpu) != k or \
-            any(i.numel() != im.shape[0] for i, im in zip(frame_idx_cpu, images)):
-        raise capi.MavlmError("video_memory_tokens_clips: one frame index tensor per video, of its length")
-    if D % 256:                                  # (refused before any step: mavlm_fuse_emit_layout_frames_to would, afterwards)
-        raise capi.MavlmError(f"video_memory_tokens_clips: the clip emit needs a hidden size that is a multiple of 256; got {D}")
-    pe: TemporalPositionalEncoding = model.positional_encoding
-    rm: TransformerProjector = model.recurrent_memory_transformer
-    order = sorted(range(k), key=lambda i: -images[i].shape[0])            # longest first; stable in the caller's order
-    xs, fines = [], []
-    for i in order:
-        pe.check_indices(frame_idx_cpu[i])
-        xs.append(pe(images[i], _device_indices(frame_idx_cpu[i], dev), indices_checked=True))      # :510-511
-        fines.append(fine_frame_indices(images[i].shape[0], fine_frames))                           # :513-522
-    bp.reset()                                                                                      # :532
-    bp.step_frames(xs)                                                                              # :534-537: one chunk each
-    eng = bp.engine(dev, dt)
-    mp = memory_prompt_embeds.to(dt).contiguous()
-    fp = frame_prompt_embeds.to(dt).contiguous()
-    nl, nl_ptr = _newline_ptr(image_newline, layout, dev, dt)
-    rows = [video_token_rows(x.shape[0], rm.num_memory_tokens, P, with_frames, chunk, fine_frames, eng.c.cache_cap, mp.shape[0],
-                             fp.shape[0], layout) for x in xs]
-    if dst_rows is not None:
-        if out is None or out.dim() != 2 or out.shape[1] != D or out.dtype != dt or not out.is_contiguous() or not out.is_cuda \
-                or len(dst_rows) != k:
-            raise capi.MavlmError(f"video_memory_tokens_clips: `dst_rows` needs {k} rows of a contiguous [out_rows,{D}] {dt} "
-                                  "GPU tensor `out`")
-        buf, dst = out, [int(dst_rows[i]) for i in order]
-    else:
-        if out is not None:
-            raise capi.MavlmError("video_memory_tokens_clips: `out` goes with `dst_rows` (the blocks differ in length)")
-        buf = torch.empty((sum(rows), D), device=dev, dtype=dt)
-        dst = [sum(rows[:j]) for j in range(k)]
-    import ctypes
-    written = (ctypes.c_int64 * k)()
-    xptrs = (capi.vp * k)(*[x.data_ptr() for x in xs])
-    n_fines = [int(f.numel()) for f in fines]
-    fine_ld = max(n_fines) + (max(n_fines) & 1)                              # (even: every index row starts 16-byte aligned)
-    fine_cpu = torch.zeros((k, fine_ld), dtype=torch.long)
-    for j, f in enumerate(fines):
-        fine_cpu[j, :f.numel()] = f
-    fine_dev = _device_indices(fine_cpu.reshape(-1), dev)                    # [k, fine_ld], one row per video
-    capi.check(capi.lib().mavlm_fuse_emit_layout_frames_to(eng.ctx, k, xptrs, fine_dev.data_ptr(), fine_ld, (capi.i32 * k)(*n_fines),
-                                                           mp.data_ptr(), mp.shape[0], fp.data_ptr(), fp.shape[0], nl_ptr,
-                                                           1 if with_frames else 0, capi.LAYOUTS[layout], buf.data_ptr(),
-                                                           buf.shape[0], (ctypes.c_int64 * k)(*dst), written, ops.stream_ptr()),
-               "mavlm_fuse_emit_layout_frames_to")
-    assert list(written) == rows
-    back = [0] * k                               # caller's position -> position in the engine's order
-    for j, i in enumerate(order):
-        back[i] = j
-    info = {"order": order, "num_memories": [1] * k, "pe_frames": [xs[back[i]] for i in range(k)],
-            "fine_idx": [fines[back[i]] for i in range(k)], "block_rows": [rows[back[i]] for i in range(k)],
-            "frame_scores": bp.frame_scores}
-    if dst_rows is not None:
-        return out, info
-    return [buf[dst[back[i]]:dst[back[i]] + rows[back[i]]] for i in range(k)], info
+    return _row_batch_tokens("clips", "video_memory_tokens_clips", model, bp, images, frame_idx_cpu, memory_prompt_embeds,
+                             frame_prompt_embeds, image_newline, with_frames, chunk, fine_frames, out, layout, dst_rows)
 
 
 def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame_idx_cpu,
@@ -541,53 +502,26 @@ def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame
                                       image_newline: Optional[torch.Tensor], with_frames: bool = True, chunk: int = 32,
                                       fine_frames: int = 32, layout: str = "one_token"):
     """`video_memory_tokens_batched` under autograd: B videos of the same length stepped together by
-    `BatchedProjector.step_train`, then the tail of `_video_memory_tokens_autograd` over all videos - the fuser MLP runs ONCE
-    over the B * n * M * 196 stacked memory rows (HIP autograd Functions); the token-type adds, the layout and the concatenation
-    are torch ops, so autograd routes the gradients of token_type_embedding, the prompt embeddings and image_newline as in the
-    reference.  Returns (tokens [B, rows, D] with grad - the bits of `video_memory_tokens_batched` -, info).
-    `frame_idx_cpu`: shared, or a list of one index tensor per video (_batch_pe_frames).  Videos of different lengths:
+    `BatchedProjector.step_train`, then the tail of the single-video training path (`_train_block`) for every video - the fuser
+    MLP runs ONCE over the B * n * M * 196 stacked memory rows (HIP autograd Functions); the token-type adds, the layout and the
+    concatenation are torch ops, so autograd routes the gradients of token_type_embedding, the prompt embeddings and
+    image_newline as in the reference.  Returns (tokens [B, rows, D] with grad - the bits of `video_memory_tokens_batched` -,
+    info).  `frame_idx_cpu`: shared, or a list of one index tensor per video.  Videos of different lengths:
     `video_memory_tokens_ragged_train`."""
     from .. import _autograd as ag
     layout_period(layout, images[0].shape[1])
-    B = bp.batch
-    if len(images) != B:
-        raise capi.MavlmError(f"video_memory_tokens_batched_train: {B} videos expected")
-    T, P, D = images[0].shape
-    for im in images:
-        if not im.is_cuda or tuple(im.shape) != (T, P, D) or im.dtype != images[0].dtype:
-            raise capi.MavlmError("video_memory_tokens_batched_train: GPU frame tokens of one shape / dtype expected")
-    pe: TemporalPositionalEncoding = model.positional_encoding
-    rm: TransformerProjector = model.recurrent_memory_transformer
-    dev, dt = images[0].device, images[0].dtype
-    xs = _batch_pe_frames(pe, images, frame_idx_cpu, T)                                     # :510-511
-    fine_cpu = fine_frame_indices(T, fine_frames)                                          # :513-522
-    bounds = uniform_segment_variant(T, chunk)                                             # :528
+    xs, fines, order, back = _prepare_row_batch("equal", "video_memory_tokens_batched_train", model, bp, images, frame_idx_cpu,
+                                                chunk, fine_frames)
     bp.reset()                                                                             # :532
-    for i in range(len(bounds) - 1):                                                       # :534-537
-        bp.step_train([x[bounds[i]:bounds[i + 1]] for x in xs])
-    n = len(bp._tcache)
-    R = rm.num_memory_tokens * P
-    temb = model.token_type_embedding.weight
+    _step_chunks(bp.step_train, xs, chunk, False)                                          # :534-537
+    B, n = bp.batch, len(bp._tcache)
+    P, D = xs[0].shape[1:]
+    R = bp.proj.num_memory_tokens * P
     mem = torch.cat(bp._tcache, dim=0)                                                     # [n * B * R, D], oldest first (:545)
-    fused = ag.fuser_mlp(model.memory_fuser, mem, temb[0], fused_gelu=True).view(n, B, R, D)       # :546-553
-    _require_newline(image_newline, layout)
-    nl = None if layout == "no_token" else image_newline.to(device=dev, dtype=dt).reshape(1, D)
-    mp, fp = memory_prompt_embeds.to(dt), frame_prompt_embeds.to(dt)
-    fine_dev = _device_indices(fine_cpu, dev)
-    toks = []
-    mem_rows = 0
-    for b in range(B):
-        mem_block = _lay_out_block(fused[:, b].reshape(n * R, D), nl, layout, P)           # :567-634
-        mem_rows = mem_block.shape[0]
-        parts = [mp, mem_block]
-        if with_frames:
-            fine = xs[b][fine_dev] + temb[1].to(dt)                                        # :513-524,554
-            parts += [fp, _lay_out_block(fine.reshape(-1, D), nl, layout, P)]
-        toks.append(torch.cat(parts, dim=0))
-    info = {"num_memories": n, "pe_frames": xs, "fine_idx": fine_cpu,
-            "memory_rows": (mp.shape[0], mp.shape[0] + (mem_rows if layout_period(layout, P) else n * R)),
-            "frame_scores": bp.frame_scores}
-    return torch.stack(toks), info
+    fused = ag.fuser_mlp(model.memory_fuser, mem, model.token_type_embedding.weight[0], fused_gelu=True).view(n, B, R, D)   # :546-553
+    nl, mp, fp = _train_tail_operands(image_newline, memory_prompt_embeds, frame_prompt_embeds, layout, xs[0])
+    toks = [_train_block(model, fused[:, b].reshape(n * R, D), xs[b], fines[b], mp, fp, nl, with_frames, layout) for b in range(B)]
+    return torch.stack(toks), _row_batch_info("equal", bp, xs, fines, [n] * B, None, order, back, mp.shape[0], layout)
 
 
 def _ragged_fuser_rows(lib, counts, R, D, inter):
@@ -611,37 +545,16 @@ def video_memory_tokens_ragged_train(model, bp: BatchedProjector, images, frame_
     in the caller's order, the info of the ragged inference call: `order`, per-video `num_memories`, `block_rows`, ...)."""
     from .. import _autograd as ag
     layout_period(layout, images[0].shape[1])
-    k = len(images)
-    if not 2 <= k <= bp.batch:
-        raise capi.MavlmError(f"video_memory_tokens_ragged_train: 2..{bp.batch} videos expected")
-    P, D = images[0].shape[1:]
-    dev, dt = images[0].device, images[0].dtype
-    for im in images:
-        if not im.is_cuda or im.dim() != 3 or tuple(im.shape[1:]) != (P, D) or im.dtype != dt or im.device != dev:
-            raise capi.MavlmError("video_memory_tokens_batched_train: GPU frame tokens [T_b, P, D] of one dtype / device expected")
-        if im.shape[0] < chunk or im.shape[0] % chunk:
-            raise capi.MavlmError(f"video_memory_tokens_ragged_train: every video length must be a positive "
-                                  f"multiple of the chunk ({chunk} frames); got {im.shape[0]}")
-    if not isinstance(frame_idx_cpu, (list, tuple)) or len(frame_idx_cpu) != k or \
-            any(i.numel() != im.shape[0] for i, im in zip(frame_idx_cpu, images)):
-        raise capi.MavlmError("video_memory_tokens_ragged_train: one frame index tensor per video, of its length")
-    pe: TemporalPositionalEncoding = model.positional_encoding
-    rm: TransformerProjector = model.recurrent_memory_transformer
-    order = sorted(range(k), key=lambda i: -images[i].shape[0])            # longest first; stable in the caller's order
-    xs, fines = [], []
-    for i in order:
-        pe.check_indices(frame_idx_cpu[i])
-        xs.append(pe(images[i], _device_indices(frame_idx_cpu[i], dev), indices_checked=True))      # :510-511
-        fines.append(fine_frame_indices(images[i].shape[0], fine_frames))                           # :513-522
-    n_fine = fines[0].numel()
-    if any(f.numel() != n_fine for f in fines):
-        raise capi.MavlmError("video_memory_tokens_ragged_train: the videos must have the same number of fine frames")
+    xs, fines, order, back = _prepare_row_batch("ragged", "video_memory_tokens_ragged_train", model, bp, images, frame_idx_cpu,
+                                                chunk, fine_frames)
+    k = len(xs)
     chunks = [x.shape[0] // chunk for x in xs]
     bp.reset()                                                                                      # :532
-    for i in range(chunks[0]):                                                                      # :534-537, per video
-        bp.step_train([x[i * chunk:(i + 1) * chunk] for x, c in zip(xs, chunks) if c > i], ragged=True)
+    _step_chunks(lambda segs: bp.step_train(segs, ragged=True), xs, chunk, True)                    # :534-537, per video
     caches = [bp.memory_cache(b) for b in range(k)]                          # per video, oldest first
     counts = [len(c) for c in caches]
+    P, D = xs[0].shape[1:]
+    rm: TransformerProjector = model.recurrent_memory_transformer
     R = rm.num_memory_tokens * P
     temb = model.token_type_embedding.weight
     fuser = model.memory_fuser
@@ -662,23 +575,10 @@ def video_memory_tokens_ragged_train(model, bp: BatchedProjector, images, frame_
             for j, (b, p) in enumerate(zip(hold, pos)):
                 place[b][p] = out_sl[j * R:(j + 1) * R]
         blocks = [torch.cat(pl, dim=0) for pl in place]
-    _require_newline(image_newline, layout)
-    nl = None if layout == "no_token" else image_newline.to(device=dev, dtype=dt).reshape(1, D)
-    mp, fp = memory_prompt_embeds.to(dt), frame_prompt_embeds.to(dt)
-    toks = []
-    for b in range(k):
-        parts = [mp, _lay_out_block(blocks[b], nl, layout, P)]                                      # :567-634
-        if with_frames:
-            fine = xs[b][_device_indices(fines[b], dev)] + temb[1].to(dt)                           # :513-524,554
-            parts += [fp, _lay_out_block(fine.reshape(-1, D), nl, layout, P)]
-        toks.append(torch.cat(parts, dim=0))
-    back = [0] * k                               # caller's position -> position in the stepping order
-    for j, i in enumerate(order):
-        back[i] = j
-    info = {"order": order, "num_memories": [counts[back[i]] for i in range(k)],
-            "pe_frames": [xs[back[i]] for i in range(k)], "fine_idx": [fines[back[i]] for i in range(k)],
-            "block_rows": [toks[back[i]].shape[0] for i in range(k)], "frame_scores": bp.frame_scores}
-    return [toks[back[i]] for i in range(k)], info
+    nl, mp, fp = _train_tail_operands(image_newline, memory_prompt_embeds, frame_prompt_embeds, layout, xs[0])
+    toks = [_train_block(model, blocks[b], xs[b], fines[b], mp, fp, nl, with_frames, layout) for b in range(k)]
+    info = _row_batch_info("ragged", bp, xs, fines, counts, [t.shape[0] for t in toks], order, back, mp.shape[0], layout)
+    return [toks[j] for j in back], info
 
 
 ROW_BATCH_SIZES = (8, 4, 2)
@@ -1019,34 +919,42 @@ def _lay_out_block(block, nl, layout, patches):
     return torch.cat((block, nl), dim=0) if layout == "one_token" else block
 
 
+def _train_tail_operands(image_newline, memory_prompt_embeds, frame_prompt_embeds, layout, x):
+    """(newline row [1, D] or None, memory prompt, frame prompt) in the dtype of the PE frames `x`, for `_train_block`"""
+    _require_newline(image_newline, layout)
+    nl = None if layout == "no_token" else image_newline.to(device=x.device, dtype=x.dtype).reshape(1, x.shape[2])
+    return nl, memory_prompt_embeds.to(x.dtype), frame_prompt_embeds.to(x.dtype)
+
+
+def _train_block(model, fused, x, fine_cpu, mp, fp, nl, with_frames, layout):
+    """One video's token block under autograd (llava_arch.py:513-524,554,567-634) from its fused memory rows [n * R, D], oldest
+    first, and its PE frames `x`: the type-embedding add of the fine frames, the layout and the concatenation are torch ops, so
+    autograd routes the gradients of token_type_embedding, the prompt embeddings and image_newline exactly as in the reference."""
+    P, D = x.shape[1:]
+    parts = [mp, _lay_out_block(fused, nl, layout, P)]                                     # :567-634
+    if with_frames:
+        temb = model.token_type_embedding.weight
+        fine = x[_device_indices(fine_cpu, x.device)] + temb[1].to(x.dtype)                # :513-524,554
+        parts += [fp, _lay_out_block(fine.reshape(-1, D), nl, layout, P)]
+    return torch.cat(parts, dim=0)
+
+
 def _video_memory_tokens_autograd(model, rm, x, fine_cpu, memory_prompt_embeds, frame_prompt_embeds, image_newline,
                                   with_frames, out, layout="one_token"):
     """Training-mode tail of video_memory_tokens (llava_arch.py:545-554,567-634): the fuser MLP runs as HIP autograd
-    Functions; the type-embedding adds, the layout and the concatenation are torch ops so that autograd routes the gradients of
-    token_type_embedding, the prompt embeddings and image_newline exactly as in the reference."""
+    Functions - without `fused_gelu`, which the row-batched tails pass -, then `_train_block`."""
     from .. import _autograd as ag
     P, D = x.shape[1], x.shape[2]
-    dt = x.dtype
-    temb = model.token_type_embedding.weight
     # engine-mode cache entries are ring views: torch.cat copies them (the graph must not alias the ring)
     mem = torch.cat(rm.memory_cache, dim=0)                                               # :545
-    fused = ag.fuser_mlp(model.memory_fuser, mem, temb[0]).reshape(-1, D)                  # :546-553
-    _require_newline(image_newline, layout)
-    nl = None if layout == "no_token" else image_newline.to(device=x.device, dtype=dt).reshape(1, D)
-    mem_block = _lay_out_block(fused, nl, layout, P)                                       # :567-634
-    parts = [memory_prompt_embeds.to(dt), mem_block]
-    n = len(rm.memory_cache)
-    R = rm.num_memory_tokens * P
-    if with_frames:
-        fine = x[_device_indices(fine_cpu, x.device)] + temb[1].to(dt)                     # :513-524,554
-        parts += [frame_prompt_embeds.to(dt), _lay_out_block(fine.reshape(-1, D), nl, layout, P)]
-    tokens = torch.cat(parts, dim=0)
+    fused = ag.fuser_mlp(model.memory_fuser, mem, model.token_type_embedding.weight[0]).reshape(-1, D)        # :546-553
+    nl, mp, fp = _train_tail_operands(image_newline, memory_prompt_embeds, frame_prompt_embeds, layout, x)
+    tokens = _train_block(model, fused, x, fine_cpu, mp, fp, nl, with_frames, layout)
     if out is not None:
         raise capi.MavlmError("video_memory_tokens: `out=` is an inference-path feature (no autograd through a "
                               "caller-owned buffer)")
-    mp_rows = memory_prompt_embeds.shape[0]
-    info = {"num_memories": n, "pe_frames": x, "fine_idx": fine_cpu,
-            "memory_rows": (mp_rows, mp_rows + (mem_block.shape[0] if layout_period(layout, P) else n * R))}
+    info = {"num_memories": len(rm.memory_cache), "pe_frames": x, "fine_idx": fine_cpu,
+            "memory_rows": _memory_rows(memory_prompt_embeds.shape[0], len(rm.memory_cache), rm.num_memory_tokens * P, layout, P)}
     return tokens, info
 
 

@@ -680,14 +680,8 @@ class TransformerProjector(nn.Module):
             self._evo_kv = []
             self._train_steps = 0
             m = (self.initial_memory + self.memory_pos_embed).to(dt).reshape(R, D)      # :123-124
-        stats = None
-        atts = [layer.memory_segment_fusion_attention for layer in self.layers]
-        kvs = ag.project_kv(atts, frames)                           # chunk K/V of all layers: one GEMM
-        for li, layer in enumerate(self.layers):                   # :132-133
-            last_layer = li == len(self.layers) - 1
-            a, stats = ag.attention_block(atts[li], m, kvs[li][0], kvs[li][1],
-                                          want_stats=last_layer and self.compute_frame_scores, patches_per_frame=P)
-            m = ag.mlp_block(layer, a)
+        kvs = ag.project_kv([layer.memory_segment_fusion_attention for layer in self.layers], frames)    # all layers: one GEMM
+        m, stats = _form_memory(ag, self, m, kvs, self.compute_frame_scores, P)
         self._memory_cache.append(m.reshape(self.num_memory_tokens, P, D))             # :152
         self._train_steps += 1
         if len(self._memory_cache) > cap:
@@ -701,8 +695,31 @@ class TransformerProjector(nn.Module):
                 hdw = 128 if att.attention_head_size <= 128 else att.attention_head_size
                 part = ops.attention_colsum(q, k, lse, att.num_attention_heads, head_dim=hdw,
                                             scale=ops.attn_scale(att.attention_head_size))
-                self.frame_attn_scores.append(part.sum(dim=0).view(F, P).mean(dim=1).to(dt))
+                self.frame_attn_scores.append(_frame_scores(part, F, P, dt))
         return self._memory_cache, self.frame_attn_scores
+
+
+def _form_memory(ag, proj, m, kvs, want_stats, P, nb=1):
+    """Memory formation of the training paths (:132-133): the layers of `proj` over the memory rows `m` ([nb * R, D], the stacked
+    rows of nb videos) and the chunk's projected K/V `kvs` (one pair per layer).  Returns (new memory rows, the (q, k, lse2) of
+    the last layer's attention for the frame scores - None without `want_stats`)."""
+    stats = None
+    for li, layer in enumerate(proj.layers):
+        a, stats = ag.attention_block(layer.memory_segment_fusion_attention, m, kvs[li][0], kvs[li][1],
+                                      want_stats=want_stats and li == len(proj.layers) - 1, patches_per_frame=P, nb=nb)
+        m = ag.mlp_block(layer, a)
+    return m, stats
+
+
+def _frame_scores(part, F, P, dt):
+    """[F] frame scores of one video from the [H, F * P] column sums of its last formation layer (:135-139)"""
+    return part.sum(dim=0).view(F, P).mean(dim=1).to(dt)
+
+
+def _first(t, n):
+    """the first n rows (videos) of a cached tensor - the tensor itself where it holds exactly n: the graph of a step over all
+    of an entry's videos then has no view node, and the gradients into the entry are summed in the order of a plain use"""
+    return t if t.shape[0] == n else t[:n]
 
 
 def ragged_fifo_plan(steps, cap):
@@ -754,7 +771,8 @@ class BatchedProjector:
     `step`; a step over k active videos runs every operator with nb = k over the first k videos' rows (k >= 2: the launches of a
     `BatchedProjector` of size k; k = 1: those of the single-video training step), and the frame scores of all k videos come from
     ONE column-sum launch (`ops.attention_colsum_batch`).  The FIFO is per video (`ragged_fifo_plan`): a finished video keeps the
-    memories of its own last steps until `reset()`.  A batch is ragged or not from its first step on."""
+    memories of its own last steps until `reset()`.  A batch is ragged or not from its first step on; the step without the
+    keyword is the same body at k = B."""
 
     def __init__(self, proj: TransformerProjector, batch: int, fused_ln_never: bool = False):
         self.fused_ln_never = bool(fused_ln_never)
@@ -774,7 +792,7 @@ class BatchedProjector:
         self._tcache = []                     # training path: the cached memories, stacked [B*R, D] graph tensors, oldest first
         self._tevo = []                       # ... and their evolution K/V projections ([B, R, Dp] views), one pair per entry
         self._tragged = None                  # training path: True / False once a batch has started ragged / not (`reset` clears)
-        self._tsteps = []                     # ragged training: the batch step of each `_tcache` entry ([k_t * R, D], k_t videos)
+        self._tsteps = []                     # training path: the batch step of each `_tcache` entry ([k_t * R, D], k_t videos)
         self._tevo_steps = []                 # ... and of each `_tevo` entry ([k, R, Dp] views, k = the videos of the step after)
 
     def engine(self, device, dtype, frames=None) -> _Engine:
@@ -809,26 +827,57 @@ class BatchedProjector:
                 self._engine.version = None
             self._engine.post_ln_probe()
 
+    def _check_prefix(self, name, k):
+        """the prefix rule of a row batch: 2 .. B videos start together, afterwards the first k of them step, k never growing"""
+        if (self._active == 0 and not 2 <= k <= self.batch) or (self._active and not 1 <= k <= self._active):
+            raise capi.MavlmError(f"BatchedProjector.{name}: 2..{self.batch} chunks at the first step of a batch, then no more than "
+                                  f"the step before ({self._active or self.batch}): the prefix of active videos never grows; got {k}")
+
+    def _check_chunks(self, name, segs, same_frames, contiguous):
+        """GPU chunks [F, P, D] of the module's P and D and one dtype - with `same_frames` of one F, else of F_b >= 1 frames each;
+        returns the frame counts"""
+        if any(t.dim() != 3 for t in segs):
+            raise capi.MavlmError(f"BatchedProjector.{name}: [F, P, D] chunks expected")
+        t0 = segs[0]
+        for t in segs:
+            if not t.is_cuda or t.shape[1:] != t0.shape[1:] or (same_frames and t.shape[0] != t0.shape[0]) or t.dtype != t0.dtype \
+                    or (contiguous and not t.is_contiguous()):
+                raise capi.MavlmError(f"BatchedProjector.{name}: {'contiguous ' if contiguous else ''}GPU chunks "
+                                      f"{'of one shape /' if same_frames else '[F_b, P, D] of one'} dtype expected")
+        Fs = [int(t.shape[0]) for t in segs]
+        if t0.shape[1] != self.proj.patch_size or t0.shape[2] != self.proj.hidden_size or min(Fs) < 1:
+            raise capi.MavlmError(f"expected [F,{self.proj.patch_size},{self.proj.hidden_size}] chunks")
+        return Fs
+
+    def _begin_step(self, name, segs, same_frames):
+        """Prelude of the inference steps: the prefix rule, the chunk checks, the mode check, the engine for the longest chunk.
+        Returns (k, frames per chunk, engine, chunk pointers)."""
+        k = len(segs)
+        self._check_prefix(name, k)
+        Fs = self._check_chunks(name, segs, same_frames, contiguous=True)
+        if self._mode == "autograd":
+            raise capi.MavlmError(f"BatchedProjector.{name}: this video batch holds autograd tensors of `step_train`: `reset()` "
+                                  "before running the inference step")
+        if self.record_attention_maps and not same_frames:
+            raise capi.MavlmError(f"BatchedProjector.{name}: attention maps of chunks with different frame counts are not provided")
+        self._mode = "engine"
+        return k, Fs, self.engine(segs[0].device, segs[0].dtype, max(Fs)), (capi.vp * k)(*[t.data_ptr() for t in segs])
+
+    def _end_step(self, k, scores):
+        """Epilogue of every step: the counters of the batch and of its first k videos, the step's frame scores"""
+        self._n += 1
+        self._active = k
+        for b in range(k):
+            self._vsteps[b] += 1
+        if scores is not None:
+            self.frame_scores.append(scores)
+
     @torch.no_grad()
     def step(self, segs):
         """one chunk of every video: segs = B tensors [F, P, D] (contiguous, same F) - or, in a ragged row batch, of the first
         len(segs) videos: 2 .. B chunks at the first step of a batch, afterwards 1 .. the count of the step before"""
-        k = len(segs)
-        if (self._active == 0 and not 2 <= k <= self.batch) or (self._active and not 1 <= k <= self._active):
-            raise capi.MavlmError(f"BatchedProjector.step: {self.batch} chunks expected (a ragged batch: 2..{self.batch} at the "
-                                  f"first step, then no more than the step before - {self._active or self.batch}); got {k}")
-        F, P, D = segs[0].shape
-        for t in segs:
-            if not t.is_cuda or tuple(t.shape) != (F, P, D) or not t.is_contiguous() or t.dtype != segs[0].dtype:
-                raise capi.MavlmError("BatchedProjector.step: contiguous GPU chunks of one shape / dtype expected")
-        if P != self.proj.patch_size or D != self.proj.hidden_size:
-            raise capi.MavlmError(f"expected [F,{self.proj.patch_size},{self.proj.hidden_size}] chunks")
-        if self._mode == "autograd":
-            raise capi.MavlmError("BatchedProjector.step: this video batch holds autograd tensors of `step_train`: `reset()` "
-                                  "before running the inference step")
-        self._mode = "engine"
-        eng = self.engine(segs[0].device, segs[0].dtype, F)
-        ptrs = (capi.vp * k)(*[t.data_ptr() for t in segs])
+        k, Fs, eng, ptrs = self._begin_step("step", segs, True)
+        F = Fs[0]
         scores = torch.empty((k, F), device=segs[0].device, dtype=segs[0].dtype) if self.compute_frame_scores else None
         record = bool(self.record_attention_maps)
         if record and torch.cuda.is_current_stream_capturing():
@@ -843,12 +892,7 @@ class BatchedProjector:
                                                           ops.stream_ptr()), "mavlm_step_batch_active")
         if record:
             self.attention_maps.append(AttentionMaps(*eng.read_maps(F, n_past, k)))
-        self._n += 1
-        self._active = k
-        for b in range(k):
-            self._vsteps[b] += 1
-        if scores is not None:
-            self.frame_scores.append(scores)
+        self._end_step(k, scores)
         return scores
 
     @torch.no_grad()
@@ -857,160 +901,58 @@ class BatchedProjector:
         clips of fewer than 32 frames whose single chunk holds all their frames.  The same prefix rule as `step`.  Returns a list
         of k [F_b] views into one padded [k, Fmax] tensor, which is appended to `frame_scores` (the entries behind a video's F_b
         are zeros the step never writes).  Equal F_b take the launches and the bits of `step`.  No attention maps."""
-        k = len(segs)
-        if (self._active == 0 and not 2 <= k <= self.batch) or (self._active and not 1 <= k <= self._active):
-            raise capi.MavlmError(f"BatchedProjector.step_frames: 2..{self.batch} chunks at the first step of a batch, then no "
-                                  f"more than the step before ({self._active or self.batch}); got {k}")
-        P, D = segs[0].shape[1:]
-        for t in segs:
-            if not t.is_cuda or t.dim() != 3 or tuple(t.shape[1:]) != (P, D) or t.shape[0] < 1 or not t.is_contiguous() or \
-                    t.dtype != segs[0].dtype:
-                raise capi.MavlmError("BatchedProjector.step_frames: contiguous GPU chunks [F_b, P, D] of one dtype expected")
-        if P != self.proj.patch_size or D != self.proj.hidden_size:
-            raise capi.MavlmError(f"expected [F,{self.proj.patch_size},{self.proj.hidden_size}] chunks")
-        if self._mode == "autograd":
-            raise capi.MavlmError("BatchedProjector.step_frames: this video batch holds autograd tensors of `step_train`: "
-                                  "`reset()` before running the inference step")
-        if self.record_attention_maps:
-            raise capi.MavlmError("BatchedProjector.step_frames: attention maps of chunks with different frame counts are not provided")
-        self._mode = "engine"
-        Fs = [int(t.shape[0]) for t in segs]
+        k, Fs, eng, ptrs = self._begin_step("step_frames", segs, False)
         Fmax = max(Fs)
-        eng = self.engine(segs[0].device, segs[0].dtype, Fmax)
         eng.set_maps(False)
-        ptrs = (capi.vp * k)(*[t.data_ptr() for t in segs])
         fv = (capi.i32 * k)(*Fs)
         scores = torch.zeros((k, Fmax), device=segs[0].device, dtype=segs[0].dtype) if self.compute_frame_scores else None
         capi.check(capi.lib().mavlm_step_batch_frames(eng.ctx, ptrs, fv, k, scores.data_ptr() if scores is not None else 0, Fmax, 0,
                                                       ops.stream_ptr()), "mavlm_step_batch_frames")
-        self._n += 1
-        self._active = k
-        for b in range(k):
-            self._vsteps[b] += 1
-        if scores is None:
-            return None
-        self.frame_scores.append(scores)
-        return [scores[b, :Fs[b]] for b in range(k)]
+        self._end_step(k, scores)
+        return None if scores is None else [scores[b, :Fs[b]] for b in range(k)]
 
     def step_train(self, segs, ragged=False):
         """One chunk of every video under autograd (see the class docstring): segs = B tensors [F, P, D] of one shape.  Mirrors
         `TransformerProjector._forward_autograd` over the stacked rows, in the launch order of `mavlm_step_batch`.  Returns the
         detached [B, F] frame scores (None with `compute_frame_scores = False`).
-        `ragged=True`: the chunks of the first len(segs) videos - 2 .. B at the first step of a batch, afterwards 1 .. the count
-        of the step before (`_step_train_ragged`); returns [len(segs), F] scores."""
-        if ragged:
-            return self._step_train_ragged(segs)
-        from ... import _autograd as ag
-        proj, B = self.proj, self.batch
-        if self.record_attention_maps:
-            raise capi.MavlmError("record_attention_maps is not supported on the autograd (training) path: attention maps are "
-                                  "recorded by inference steps only")
-        if len(segs) != B:
-            raise capi.MavlmError(f"BatchedProjector.step_train: {B} chunks expected")
-        if any(t.dim() != 3 for t in segs):
-            raise capi.MavlmError("BatchedProjector.step_train: [F, P, D] chunks expected")
-        F, P, D = segs[0].shape
-        for t in segs:
-            if not t.is_cuda or tuple(t.shape) != (F, P, D) or t.dtype != segs[0].dtype:
-                raise capi.MavlmError("BatchedProjector.step_train: GPU chunks of one shape / dtype expected")
-        if P != proj.patch_size or D != proj.hidden_size or F < 1:
-            raise capi.MavlmError(f"expected [F,{proj.patch_size},{proj.hidden_size}] chunks")
-        if self._mode == "engine":
-            raise capi.MavlmError("BatchedProjector.step_train: this video batch was started by the inference `step`: `reset()` "
-                                  "before running the training path")
-        if self._tragged:
-            raise capi.MavlmError("BatchedProjector.step_train: this video batch was started as a ragged row batch "
-                                  "(`ragged=True`): `reset()` before stepping it without the keyword")
-        self._mode = "autograd"
-        self._tragged = False
-        proj._train_state["epoch"] += 1          # an optimizer step may follow: packed copies are suspect afterwards
-        dt = segs[0].dtype
-        M = proj.num_memory_tokens
-        R = M * P
-        S = F * P
-        cap = int(getattr(proj.config, "cache_cap", 10))
-        evo = proj.memory_update_attention
-        if self._tcache:                                            # memory evolution (MemoryController.py:89-97, 125-127)
-            # each cached memory is projected once, when it is the newest: one packed GEMM over the stacked rows of all videos
-            while len(self._tevo) < len(self._tcache):
-                self._tevo.append(ag.project_kv([evo], self._tcache[len(self._tevo)], nb=B)[0])
-            # keys of a video in the slot order of the inference ring (memory g lives in slot g % cap): the attention sums in
-            # the same order after the FIFO has wrapped
-            first = self._n - len(self._tevo)
-            order = sorted(range(len(self._tevo)), key=lambda i: (first + i) % cap)
-            k = torch.cat([self._tevo[i][0] for i in order], dim=1)                    # [B, n*R, Dp]
-            v = torch.cat([self._tevo[i][1] for i in order], dim=1)
-            m, _ = ag.attention_block(evo, self._tcache[-1], k, v, nb=B)
-        else:
-            self._tevo = []
-            m = (proj.initial_memory + proj.memory_pos_embed).to(dt).reshape(R, D).repeat(B, 1)      # :123-124, every video
-        atts = [layer.memory_segment_fusion_attention for layer in proj.layers]
-        kvs = self._chunk_kv(ag, atts, segs, S, D)
-        stats = None
-        for li, layer in enumerate(proj.layers):                    # memory formation (:132-133)
-            last_layer = li == len(proj.layers) - 1
-            a, stats = ag.attention_block(atts[li], m, kvs[li][0], kvs[li][1], want_stats=last_layer and self.compute_frame_scores,
-                                          patches_per_frame=P, nb=B)
-            m = ag.mlp_block(layer, a)
-        self._tcache.append(m)                                      # :152
-        self._n += 1
-        self._vsteps = [v + 1 for v in self._vsteps]
-        if len(self._tcache) > cap:
-            drop = len(self._tcache) - cap
-            self._tcache = self._tcache[drop:]
-            self._tevo = self._tevo[drop:]
-        scores = None
-        if stats is not None:                                       # :135-139, 156 (detached statistics)
-            scores = self._train_frame_scores(stats, atts[-1], F, P, R, dt)
-            self.frame_scores.append(scores)
-        return scores
-
-    def _step_train_ragged(self, segs):
-        """`step_train(ragged=True)`: one chunk of the first k = len(segs) videos (longest first; the prefix only shrinks).  Rows
-        [:k*R] of the newest cached memory and [:k] of the cached evolution K/V are the active videos'; a cached memory is
-        projected for the evolution over the rows of the videos that step again only."""
+        `ragged=True`: the chunks of the first len(segs) videos (longest first) - 2 .. B at the first step of a batch, afterwards
+        1 .. the count of the step before; returns [len(segs), F] scores.  One body serves both: the equal-length step is the
+        ragged step over k = B videos.  Rows [:k*R] of the newest cached memory and [:k] of the cached evolution K/V are the active
+        videos'; a cached memory is projected for the evolution over the rows of the videos that step again only."""
         from ... import _autograd as ag
         proj, B = self.proj, self.batch
         k = len(segs)
         if self.record_attention_maps:
             raise capi.MavlmError("record_attention_maps is not supported on the autograd (training) path: attention maps are "
                                   "recorded by inference steps only")
-        if self._mode == "engine":
-            raise capi.MavlmError("BatchedProjector.step_train: this video batch was started by the inference `step`: `reset()` "
-                                  "before running the training path")
-        if self._tragged is False:
-            raise capi.MavlmError("BatchedProjector.step_train(ragged=True): this video batch was started without the keyword: "
-                                  "`reset()` before stepping it as a ragged row batch")
-        if (self._active == 0 and not 2 <= k <= B) or (self._active and not 1 <= k <= self._active):
-            raise capi.MavlmError(f"BatchedProjector.step_train(ragged=True): 2..{B} chunks at the first step of a batch, then no "
-                                  f"more than the step before ({self._active or B}): the prefix of active videos never grows; "
-                                  f"got {k}")
-        if any(t.dim() != 3 for t in segs):
-            raise capi.MavlmError("BatchedProjector.step_train: [F, P, D] chunks expected")
-        F, P, D = segs[0].shape
-        for t in segs:
-            if not t.is_cuda or tuple(t.shape) != (F, P, D) or t.dtype != segs[0].dtype:
-                raise capi.MavlmError("BatchedProjector.step_train: GPU chunks of one shape / dtype expected")
-        if P != proj.patch_size or D != proj.hidden_size or F < 1:
-            raise capi.MavlmError(f"expected [F,{proj.patch_size},{proj.hidden_size}] chunks")
-        self._mode = "autograd"
-        self._tragged = True
+        if ragged:
+            self._check_train_mode(True)
+            self._check_prefix("step_train(ragged=True)", k)
+        elif k != B:
+            raise capi.MavlmError(f"BatchedProjector.step_train: {B} chunks expected")
+        F = self._check_chunks("step_train", segs, True, contiguous=False)[0]
+        if not ragged:
+            self._check_train_mode(False)
+        self._mode, self._tragged = "autograd", bool(ragged)
         proj._train_state["epoch"] += 1          # an optimizer step may follow: packed copies are suspect afterwards
         dt = segs[0].dtype
+        P, D = proj.patch_size, proj.hidden_size
         R = proj.num_memory_tokens * P
-        S = F * P
         cap = int(getattr(proj.config, "cache_cap", 10))
         evo = proj.memory_update_attention
         n = self._n                                                 # this step's index: the same for every video that takes it
         if self._tcache:                                            # memory evolution (MemoryController.py:89-97, 125-127)
-            newest = self._tcache[-1][:k * R]                       # (step n - 1: video 0 holds it)
-            kv = ag.project_kv([evo], newest, nb=k)[0]              # one packed GEMM over the rows of the videos that step again
+            # each cached memory is projected once, when it is the newest (step n - 1: video 0 holds it): one packed GEMM over
+            # the stacked rows of the videos that step again
+            newest = _first(self._tcache[-1], k * R)
+            kv = ag.project_kv([evo], newest, nb=k)[0]
             self._tevo.append(kv if k > 1 else (kv[0].unsqueeze(0), kv[1].unsqueeze(0)))
             self._tevo_steps.append(n - 1)
-            # keys of a video in the slot order of the inference ring (memory g lives in slot g % cap)
+            # keys of a video in the slot order of the inference ring (memory g lives in slot g % cap): the attention sums in
+            # the same order after the FIFO has wrapped
             order = sorted(range(len(self._tevo)), key=lambda i: self._tevo_steps[i] % cap)
-            kk = torch.cat([self._tevo[i][0][:k] for i in order], dim=1)               # [k, n*R, Dp]
-            vv = torch.cat([self._tevo[i][1][:k] for i in order], dim=1)
+            kk = torch.cat([_first(self._tevo[i][0], k) for i in order], dim=1)        # [k, n*R, Dp]
+            vv = torch.cat([_first(self._tevo[i][1], k) for i in order], dim=1)
             if k == 1:
                 kk, vv = kk[0], vv[0]
             m, _ = ag.attention_block(evo, newest, kk, vv, nb=k)
@@ -1018,45 +960,43 @@ class BatchedProjector:
             self._tevo, self._tevo_steps = [], []
             m = (proj.initial_memory + proj.memory_pos_embed).to(dt).reshape(R, D).repeat(k, 1)      # :123-124, every video
         atts = [layer.memory_segment_fusion_attention for layer in proj.layers]
-        kvs = self._chunk_kv(ag, atts, segs, S, D, nb=k)
-        stats = None
-        for li, layer in enumerate(proj.layers):                    # memory formation (:132-133)
-            last_layer = li == len(proj.layers) - 1
-            a, stats = ag.attention_block(atts[li], m, kvs[li][0], kvs[li][1], want_stats=last_layer and self.compute_frame_scores,
-                                          patches_per_frame=P, nb=k)
-            m = ag.mlp_block(layer, a)
+        m, stats = _form_memory(ag, proj, m, self._chunk_kv(ag, atts, segs, F * P, D, k), self.compute_frame_scores, P, nb=k)
+        scores = None
+        if stats is not None:                                       # :135-139, 156 (detached statistics)
+            with torch.no_grad():                                   # one column-sum launch for all k videos
+                q, kl, lse = stats
+                H, hd = atts[-1].num_attention_heads, atts[-1].attention_head_size
+                part = ops.attention_colsum_batch(q, kl if k > 1 else kl.unsqueeze(0), lse, H, k, head_dim=128 if hd <= 128 else hd,
+                                                  scale=ops.attn_scale(hd))
+                # (finished per video with the single-video path's torch ops on its [H, S] plane: the same bits)
+                scores = torch.stack([_frame_scores(part[b], F, P, dt) for b in range(k)])
         self._tcache.append(m)                                      # :152
         self._tsteps.append(n)
-        self._n += 1
-        self._active = k
-        for b in range(k):
-            self._vsteps[b] += 1
-        # per-video FIFO: an entry goes once no video - finished ones included - holds its step; the evolution reads the active
-        # videos' last `cap` steps only
+        self._end_step(k, scores)
+        # per-video FIFO: an entry goes once no video - finished ones included - holds its step (equal lengths: the oldest, once
+        # there are more than `cap`); the evolution reads the active videos' last `cap` steps only
         _, gone = ragged_fifo_plan(self._vsteps, cap)
         if gone:
             keep = [i for i, t in enumerate(self._tsteps) if t not in set(gone)]
             self._tcache, self._tsteps = [self._tcache[i] for i in keep], [self._tsteps[i] for i in keep]
         while self._tevo_steps and self._tevo_steps[0] <= self._n - cap - 1:
             self._tevo, self._tevo_steps = self._tevo[1:], self._tevo_steps[1:]
-        scores = None
-        if stats is not None:                                       # :135-139, 156 (detached statistics)
-            with torch.no_grad():
-                q, kl, lse = stats
-                H, hd = atts[-1].num_attention_heads, atts[-1].attention_head_size
-                part = ops.attention_colsum_batch(q, kl if k > 1 else kl.unsqueeze(0), lse, H, k, head_dim=128 if hd <= 128 else hd,
-                                                  scale=ops.attn_scale(hd))
-                # (finished per video with the single-video path's torch ops on its [H, S] plane: the same bits)
-                scores = torch.stack([part[b].sum(dim=0).view(F, P).mean(dim=1).to(dt) for b in range(k)])
-            self.frame_scores.append(scores)
         return scores
 
-    def _chunk_kv(self, ag, atts, segs, S, D, nb=None):
-        """K/V of the chunk for all layers as [B, S, W] views: ONE GEMM over the stacked frames where that gives the bits of the
-        step's per-video GEMMs (row-independent kernels; only a split contraction - `mavlm_linear_ws_floats`, a function of
-        the row count - sums in another order), else one GEMM per video as the step runs them.  `nb`: the videos of a ragged
-        step (default: the whole batch); one video gives the single-video step's [S, W] views."""
-        B = self.batch if nb is None else nb
+    def _check_train_mode(self, ragged):
+        """a video batch runs in one mode, and under autograd ragged or not, from its first step to `reset()`"""
+        if self._mode == "engine":
+            raise capi.MavlmError("BatchedProjector.step_train: this video batch was started by the inference `step`: `reset()` "
+                                  "before running the training path")
+        if self._tragged is not None and self._tragged != bool(ragged):
+            raise capi.MavlmError(f"BatchedProjector.step_train: this video batch was started {'with' if self._tragged else 'without'} "
+                                  f"`ragged=True`: `reset()` before stepping it {'with' if ragged else 'without'} the keyword")
+
+    def _chunk_kv(self, ag, atts, segs, S, D, B):
+        """K/V of the chunk of B videos for all layers as [B, S, W] views: ONE GEMM over the stacked frames where that gives the
+        bits of the step's per-video GEMMs (row-independent kernels; only a split contraction - `mavlm_linear_ws_floats`, a
+        function of the row count - sums in another order), else one GEMM per video as the step runs them.  One video gives the
+        single-video step's [S, W] views."""
         if B == 1:
             return ag.project_kv(atts, segs[0].detach().reshape(S, D))
         frames = [t.detach().reshape(S, D) for t in segs]           # frame features carry no gradient (llava_arch.py:302)
@@ -1068,29 +1008,14 @@ class BatchedProjector:
         per = [ag.project_kv(atts, f) for f in frames]
         return [(torch.stack([p[i][0] for p in per]), torch.stack([p[i][1] for p in per])) for i in range(len(atts))]
 
-    @torch.no_grad()
-    def _train_frame_scores(self, stats, att, F, P, R, dt):
-        """[B, F] frame scores of the last formation layer from its saved (q, k, lse2): the column-sum pass per video, exactly as
-        the single-video training path runs it (MemoryController.py:135-139)."""
-        q, k, lse = stats
-        H, hd = att.num_attention_heads, att.attention_head_size
-        out = []
-        for b in range(self.batch):
-            part = ops.attention_colsum(q[b * R:(b + 1) * R], k[b], lse[b * H:(b + 1) * H], H, head_dim=128 if hd <= 128 else hd,
-                                        scale=ops.attn_scale(hd))
-            out.append(part.sum(dim=0).view(F, P).mean(dim=1).to(dt))
-        return torch.stack(out)
-
     def memory_cache(self, b: int) -> List[torch.Tensor]:
         """video b's FIFO, oldest first: ring views after `step` (as TransformerProjector.memory_cache), graph-carrying
         [M, P, D] tensors after `step_train`"""
-        if self._mode == "autograd":
+        if self._mode == "autograd":         # video b's own last steps: entry t holds the rows of the k_t videos of step t
             proj = self.proj
-            if self._tragged:                # video b's own last steps: entry t holds the rows of the k_t videos of step t
-                held = set(ragged_fifo_plan(self._vsteps, int(getattr(proj.config, "cache_cap", 10)))[0][b])
-                return [m.view(-1, proj.num_memory_tokens, proj.patch_size, proj.hidden_size)[b]
-                        for m, t in zip(self._tcache, self._tsteps) if t in held]
-            return [m.view(self.batch, proj.num_memory_tokens, proj.patch_size, proj.hidden_size)[b] for m in self._tcache]
+            held = set(ragged_fifo_plan(self._vsteps, int(getattr(proj.config, "cache_cap", 10)))[0][b])
+            return [m.view(-1, proj.num_memory_tokens, proj.patch_size, proj.hidden_size)[b]
+                    for m, t in zip(self._tcache, self._tsteps) if t in held]
         eng = self._engine
         cap = eng.c.cache_cap
         steps = self._vsteps[b]              # (video b's own steps: a ragged row batch leaves its ring rows as its last step did)

@@ -343,6 +343,47 @@ def test_ragged_token_block_forward_and_gradients(layout):
     assert not fails, fails
 
 
+# ---- 6b. the equal-length step is the ragged step at k = B ------------------------------------------------------------------------------
+def test_equal_length_step_is_the_ragged_step_at_k_equal_B():
+    """3 videos of 4 chunks each on a batch of 3, FIFO of 2 (it wraps twice): `step_train(segs)` and, after `reset()`,
+    `step_train(segs, ragged=True)` give the same memories of every video at every step, the same frame scores and - after one
+    backward pass of the same scalar - the same gradients of `initial_memory`, an evolution-attention weight and a formation-layer
+    weight, all bit for bit: a step over all videos of a cached entry uses the entry itself (no view node), so the graphs agree."""
+    st = _setup("bf16")
+    rm = st.rm
+    chunks = [4, 4, 4]
+    _, xs = _videos(st, chunks, 7800)
+    cots = _cots(st, chunks, 7400)
+    watch = ["initial_memory", "memory_update_attention.q_proj.weight", "layers.0.mlp.0.weight"]
+    params = dict(rm.named_parameters())
+    bp = BatchedProjector(rm, 3)
+    runs = []
+    for kw in ({}, {"ragged": True}):
+        rm.zero_grad(set_to_none=True)
+        bp.reset()
+        mems = []
+        for i in range(chunks[0]):
+            sc = bp.step_train(_segs(xs, chunks, i), **kw)
+            assert tuple(sc.shape) == (3, CHUNK)
+            mems.append([[m.detach().clone() for m in bp.memory_cache(b)] for b in range(3)])
+        assert bp._tragged is bool(kw) and all(len(c) == CAP for c in mems[-1])
+        scores = [s.clone() for s in bp.frame_scores]
+        _loss(bp, cots, range(3)).backward()
+        bp.reset()
+        runs.append((mems, scores, {k: params[k].grad.clone() for k in watch}))
+    rm.zero_grad(set_to_none=True)
+    (ma, sa, ga), (mb, sb, gb) = runs
+    for t, (a, b) in enumerate(zip(ma, mb)):
+        for v in range(3):
+            assert len(a[v]) == len(b[v]) == min(t + 1, CAP)
+            for x, y in zip(a[v], b[v]):
+                assert torch.equal(x, y), f"step {t} video {v}: memory"
+    assert len(sa) == len(sb) == 4 and all(torch.equal(x, y) for x, y in zip(sa, sb)), "frame scores"
+    for k in watch:
+        assert torch.isfinite(ga[k].float()).all() and ga[k].float().abs().sum() > 0, k
+        assert torch.equal(ga[k], gb[k]), f"{k}: gradient of the equal-length step differs from the ragged step's at k = B"
+
+
 # ---- 7. refusals -----------------------------------------------------------------------------------------------------------------------
 def test_refusals():
     st = _setup("bf16")
