@@ -4,7 +4,7 @@ backward are the HIP kernels of this library.  The reference trains the same mod
 graph and routes gradients - every product, softmax, normalisation and activation runs in csrc/.
 
 The forward of each Function issues exactly the kernel sequence of the fused inference step (`mavlm_step`,
-csrc/mavlm_api.hip), so training-mode activations are bit-identical to inference-mode ones (tested).
+csrc/mavlm_step.hip), so training-mode activations are bit-identical to inference-mode ones (tested).
 Gradients are produced in the parameter dtype (bf16 / fp16), as autograd does for the reference under
 `--bf16 True`; reductions (dW contraction, bias / LayerNorm-affine sums) accumulate in fp32 before the one rounding.
 """

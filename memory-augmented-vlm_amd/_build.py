@@ -4,8 +4,8 @@ import shutil
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["gemm.hip", "gemm256.hip", "gemm256p.hip", "gemm128.hip", "attention.hip", "attention3.hip", "attention_hd.hip", "attention_maps.hip", "attention_bwd.hip", "attention_bwd_hd.hip", "backward.hip", "variants.hip", "elementwise.hip", "mavlm_api.hip", "prof.hip"]
-HEADERS = ["mavlm_common.h", "mavlm_kernels.h", os.path.join("..", "..", "include", "mavlm.h")]
+SOURCES = ["gemm.hip", "gemm256.hip", "gemm256p.hip", "gemm128.hip", "attention.hip", "attention3.hip", "attention_hd.hip", "attention_maps.hip", "attention_bwd.hip", "attention_bwd_hd.hip", "backward.hip", "variants.hip", "elementwise.hip", "mavlm_context.hip", "mavlm_step.hip", "mavlm_emit.hip", "mavlm_ops.hip", "prof.hip"]
+HEADERS = ["mavlm_common.h", "mavlm_kernels.h", "mavlm_ctx.h", os.path.join("..", "..", "include", "mavlm.h")]
 
 
 def library_path() -> str:

@@ -17,7 +17,7 @@ def dtype_code(dt: torch.dtype) -> int:
 
 
 def attn_scale(head_dim: int) -> float:
-    """1/sqrt(head_dim) exactly as the C side computes it (`1.0f / sqrtf((float)hd)`, csrc/mavlm_api.hip): float32
+    """1/sqrt(head_dim) exactly as the C side computes it (`1.0f / sqrtf((float)hd)`, csrc/mavlm_ctx.h): float32
     square root, float32 division - so the training path and the fused inference step hand the kernels the same bits."""
     import numpy as np
     return float(np.float32(1.0) / np.sqrt(np.float32(head_dim)))

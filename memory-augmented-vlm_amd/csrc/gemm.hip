@@ -11,7 +11,7 @@
 // columns of one row -> 8-byte (16-bit out) / 16-byte (fp32 out) epilogue stores.
 //
 // Ragged M is allowed (row loads are clamped to M-1, stores masked); N % 128 == 0 and K % 64 == 0 required
-// (checked on the host in mavlm_api.hip).
+// (checked on the host in mavlm_ops.hip).
 #include "mavlm_common.h"
 #include "mavlm_kernels.h"
 

@@ -1,4 +1,4 @@
-// Internal launch interface between the C-ABI layer (mavlm_api.hip) and the kernel translation units.
+// Internal launch interface between the host layer (mavlm_ctx.h and the mavlm_{context,step,emit,ops}.hip units) and the kernel translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -95,6 +95,8 @@ extern int g_mavlm_gemm_tile;   // 0 = auto, 128 / 256 = forced non-persistent, 
 // height of the 256-column workgroup tile for an M x N output: 256 or 224 rows (gemm256.hip); same results either way
 int mavlm_gemm_tile_rows(int M, int N);
 extern int g_mavlm_gemm_rows;   // 0 = auto, 224 / 256 = forced (tuning hook)
+extern int g_mavlm_gemm_order;              // gemm256p.hip (mavlm_set_gemm_order)
+extern int g_mavlm_gemm_f32_short_splits;   // gemm.hip (mavlm_set_gemm_short_splits)
 
 struct mavlm_attn_args {
   const void* Q; int ldq;        // [R, >=H*128] 16-bit; head h at column h*128
@@ -162,6 +164,8 @@ int mavlm_attention_hd_splits(int R, int S, int H, int* tiles_per_split);
 size_t mavlm_attention_hd_split_ws_floats(int R, int S, int H, int head_dim);
 int mavlm_attention_hd_streamk(int R, int S, int H, int head_dim, int info[3]);
 extern int g_mavlm_attn_sk_min_tiles;   // attention3.hip: key tiles (of 64) a unit needs before the stream-K schedules apply
+extern int g_mavlm_attn_sk_waves;       // attention3.hip (mavlm_set_attention_streamk_waves)
+extern int g_mavlm_attn_unit_order;     // attention3.hip (mavlm_set_attention_unit_order)
 hipError_t mavlm_launch_attention_combine(const float* opart, const float* lpart, void* O, int ldo, float* lse2, int R, int H,
                                           int hd, int ns, int dtype, hipStream_t s);
 // software-pipelined LDS-DMA variant (attention3.hip); mavlm_launch_attention dispatches to it
@@ -191,6 +195,7 @@ struct mavlm_attn_bwd_args {
   long long kv_bstride = 0, dkv_bstride = 0;
 };
 hipError_t mavlm_launch_attention_bwd(const mavlm_attn_bwd_args& a, int dtype, hipStream_t s);
+extern int g_mavlm_attn_bwd_fused;      // attention_bwd.hip (mavlm_set_attention_bwd_fused)
 // the same for head_dim 448 (attention_bwd_hd.hip); O / dO / dQ / dK / dV are [rows, H*448]
 hipError_t mavlm_launch_attention_bwd_hd(const mavlm_attn_bwd_args& a, int head_dim, int dtype, hipStream_t s);
 

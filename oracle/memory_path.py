@@ -451,7 +451,7 @@ def streamk_split_tiles(R: int, S: int, heads: int):
 
 
 def frame_scores_fused(R: int, S: int, heads: int, patches: int, head_dim: int = 128) -> bool:
-    """Mirrors mavlm_frame_scores_fused (csrc/mavlm_api.hip) for head_dim <= 128: does the fused step compute the frame
+    """Mirrors mavlm_frame_scores_fused (csrc/mavlm_ops.hip) for head_dim <= 128: does the fused step compute the frame
     scores inside the last formation layer's forward?  (Round 3: that launch runs the same schedule as the plain forward
     of the shape, so the answer no longer changes the rounding plan - kept for the tests of the C function.)"""
     return bool(FRAME_SCORES_FUSED and head_dim <= 128 and patches % 4 == 0 and patches >= KV_TILE and S > 0 and
@@ -531,7 +531,7 @@ LAZY_SCORE_ELEMS = 1 << 27  # ... and above which a block's scores are produced 
 # Heads and query blocks are independent: large problems spread them over a few threads (numpy releases the GIL inside
 # its kernels).  Same operations on the same data in the same order per head / block - results do not depend on it.
 FRAME_SCORES_FUSED = True        # mirror of mavlm_set_frame_score_mode (1 = default)
-# Row batch (mavlm_config.batch, csrc/mavlm_api.hip): (b, B) = this computation is video b of B stepped together.  The
+# Row batch (mavlm_config.batch, csrc/mavlm_step.hip): (b, B) = this computation is video b of B stepped together.  The
 # arithmetic of a video does not change - only the attention SCHEDULE does: the stream-K plan is laid over B * heads
 # "heads" (video-major), the small grids' split-KV form is not used.  (0, 1) = a single video.
 ROW_BATCH = (0, 1)

@@ -76,5 +76,5 @@ open(p,'w').write(s)
 EOF
 mkdir -p "$ROOT/memory-augmented-vlm_amd/lib/exp"
 # (a failed build fails the script: no pipe that swallows hipcc's status)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -o "$ROOT/memory-augmented-vlm_amd/lib/exp/libmavlm_stamps.so" gemm.hip gemm256.hip gemm256p.hip attention.hip attention3.hip attention_hd.hip attention_bwd.hip backward.hip variants.hip elementwise.hip mavlm_api.hip prof.hip
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -o "$ROOT/memory-augmented-vlm_amd/lib/exp/libmavlm_stamps.so" gemm.hip gemm256.hip gemm256p.hip attention.hip attention3.hip attention_hd.hip attention_bwd.hip backward.hip variants.hip elementwise.hip mavlm_context.hip mavlm_step.hip mavlm_emit.hip mavlm_ops.hip prof.hip
 ls -la "$ROOT/memory-augmented-vlm_amd/lib/exp/libmavlm_stamps.so"
