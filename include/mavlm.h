@@ -191,6 +191,8 @@ int mavlm_step_batch_active(mavlm_ctx* ctx, const void* const* segs, int32_t n_a
  * variable-length column sums (mavlm_attention_colsum_batch_varlen; 448: the per-video pass) and the finishing kernel, never from
  * the forward - the memory is the same bits with and without frame_scores and under every mavlm_set_frame_score_mode.  The
  * column sums of all videos use a scratch region of their own behind every other one (no offset of mavlm_workspace_layout moves).
+ * Under autograd the same step is composed on the host from the stand-alone operators (BatchedProjector.step_train_frames): the
+ * variable-length forward above, its backward mavlm_attention_bwd_batch_varlen and the variable-length column sums.
  * MAVLM_E_ARG: n_active outside 1 .. B, n_active > 16 with unequal F, an F[b] outside its range, ld_scores too small;
  * MAVLM_E_STATE: a single-video context, a growing prefix, attention maps bound while the F differ. */
 int mavlm_step_batch_frames(mavlm_ctx* ctx, const void* const* segs, const int32_t* F, int32_t n_active, void* frame_scores,
@@ -544,6 +546,22 @@ int mavlm_attention_bwd_hd_batch(const void* Q, int32_t ldq, const void* K, int3
                                  void* dQ, int32_t lddq, void* dK, int32_t lddk, void* dV, int32_t lddv, int32_t R, int32_t S,
                                  int32_t H, int32_t head_dim, float scale, int32_t nb, int64_t kv_bstride, int64_t dkv_bstride,
                                  int32_t dtype, void* stream);
+/* The backward of mavlm_attention_batch_varlen (heads of <= 128 columns): video b has its own S[b] >= 1 keys, which start
+ * kv_off[b] elements into K and V; its key gradients start dkv_off[b] elements into dK and dV.  S, kv_off and dkv_off are HOST
+ * arrays of nb <= 16 entries, read during the call (they reach the kernels by value).  Everything else as in
+ * mavlm_attention_bwd_batch: H heads of all videos, Q / O / dO / dQ [nb*R, ...] video after video, lse2 / delta [H, R]; null
+ * dQ / dK / dV skip that gradient (dkv_off is not read when both dK and dV are null).  Keys may be packed back to back: no read
+ * and no store crosses a video's last key, rows of dK / dV outside the videos' ranges are left untouched, every output row has
+ * one owner and no atomics are used - video b's rows of dQ / dK / dV equal, bit for bit, mavlm_attention_bwd on that video's own
+ * operands.  Always one kernel per gradient (mavlm_set_attention_bwd_fused is not consulted).  Checks before anything is
+ * enqueued: MAVLM_E_ARG for a null required pointer, nb < 1, nb > 16, H % nb != 0, S[b] < 1, offsets that are negative or no
+ * multiple of 8, ranges [off[b], off[b] + S[b] * ld) that overlap (kv_off by ldk or ldv, dkv_off by lddk or lddv), misaligned
+ * or too narrow operands, a video whose keys exceed the kernels' 32-bit offsets; MAVLM_E_SHAPE for head_dim outside 1..128. */
+int mavlm_attention_bwd_batch_varlen(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, const void* O,
+                                     int32_t ldo, const void* dO, int32_t lddo, const float* lse2, float* delta, void* dQ,
+                                     int32_t lddq, void* dK, int32_t lddk, void* dV, int32_t lddv, int32_t R, const int32_t* S,
+                                     const int64_t* kv_off, const int64_t* dkv_off, int32_t H, float scale, int32_t nb,
+                                     int32_t head_dim, int32_t dtype, void* stream);
 /* C[M,N] 16-bit = A[M,K] . W[N,K]^T, contraction split over `splits` workgroup planes; ws = splits*M*N fp32;
  * zero_bias = N fp32 zeros.  For dW = dY^T X, whose contraction runs over all rows of the activations. */
 int mavlm_linear_splitk(const void* A, int32_t lda, const void* W, int32_t ldw, void* C, int32_t M, int32_t N, int32_t K,

@@ -127,12 +127,20 @@ class AttentionFn(torch.autograd.Function):
     """ctx = softmax(q k^T * scale) v per head (MemoryController.py:51-54), heads of 128 columns (narrower heads are
     zero-padded by the caller).  Saves O and the log-sum-exp; the backward recomputes the probabilities per tile.
     `nb` > 1: a row batch - q holds the query rows of nb videos one after the other, k / v are [nb, S, W] views (`heads` per
-    video); forward and backward are ONE launch each over the (video, head) pairs, on the schedule of `mavlm_step_batch`."""
+    video); forward and backward are ONE launch each over the (video, head) pairs, on the schedule of `mavlm_step_batch`.
+    `key_counts` (a tuple, heads of <= 128 columns): a variable-length row batch - video b has key_counts[b] keys, k / v are
+    [sum(key_counts), W] with the videos' keys packed back to back; the plain grid per video, forward and backward (`nb` is
+    not read: the videos are counted by the tuple)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, heads, scale, head_dim=128, plain=False, nb=1):
+    def forward(ctx, q, k, v, heads, scale, head_dim=128, plain=False, nb=1, key_counts=None):
         q, k, v = q.detach(), k.detach(), v.detach()
-        if nb > 1:
+        ctx.key_counts = tuple(int(s) for s in key_counts) if key_counts is not None else None
+        if key_counts is not None:
+            if head_dim != 128:
+                raise capi.MavlmError(f"variable-length attention: head width {head_dim} (heads of <= 128 columns only)")
+            o, lse = ops.attention_batch_varlen(q, k, v, heads, ctx.key_counts, want_lse=True, scale=scale)
+        elif nb > 1:
             o, lse = ops.attention_batch(q, k, v, heads, nb, want_lse=True, scale=scale, head_dim=head_dim)
         else:
             o, lse = ops.attention(q, k, v, heads, want_lse=True, scale=scale, head_dim=head_dim, plain=plain)
@@ -145,7 +153,10 @@ class AttentionFn(torch.autograd.Function):
     def backward(ctx, do, _dlse):
         q, k, v, o, lse = ctx.saved_tensors
         n = ctx.needs_input_grad
-        if ctx.nb > 1:
+        if ctx.key_counts is not None:
+            dq, dk, dv = ops.attention_bwd_batch_varlen(q, k, v, o, _c(do), lse, ctx.heads, ctx.key_counts, n[0], n[1], n[2],
+                                                        scale=ctx.scale)
+        elif ctx.nb > 1:
             if ctx.head_dim not in (128, 448):
                 raise capi.MavlmError(f"row-batched attention backward: head width {ctx.head_dim} (128 or 448)")
             dq, dk, dv = ops.attention_bwd_batch(q, k, v, o, _c(do), lse, ctx.heads, ctx.nb, n[0], n[1], n[2], scale=ctx.scale,
@@ -154,7 +165,7 @@ class AttentionFn(torch.autograd.Function):
             dq, dk, dv = ops.attention_bwd(q, k, v, o, _c(do), lse, ctx.heads, n[0], n[1], n[2], scale=ctx.scale)
         else:       # wide heads (448): one head's scores at a time, every product a GEMM (ops.attention_bwd_wide)
             dq, dk, dv = ops.attention_bwd_wide(q, k, v, o, _c(do), lse, ctx.heads, ctx.head_dim, ctx.scale, n[0], n[1], n[2])
-        return dq, dk, dv, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 def head_width(hd):
@@ -204,10 +215,12 @@ def project_kv(attns, x, nb=1):
     return [(kv[:, (2 * i) * Dp:(2 * i + 1) * Dp], kv[:, (2 * i + 1) * Dp:(2 * i + 2) * Dp]) for i in range(len(attns))]
 
 
-def attention_block(attn, q_in, k, v, want_stats=False, patches_per_frame=196, nb=1):
+def attention_block(attn, q_in, k, v, want_stats=False, patches_per_frame=196, nb=1, key_counts=None):
     """`Attention.forward` (MemoryController.py:47-56) on a 2-D [rows, D] query input and already projected K/V
     (padded-head layout; may be column views); returns (out, (q, k, lse) | None).  `nb` > 1: the stacked rows of nb videos
-    and [nb, S, W] keys / values - every GEMM and LayerNorm runs once over all rows, the attention over (video, head) pairs."""
+    and [nb, S, W] keys / values - every GEMM and LayerNorm runs once over all rows, the attention over (video, head) pairs.
+    `key_counts`: the stacked rows of len(key_counts) videos and PACKED [sum(key_counts), W] keys / values, video b attending to
+    its own key_counts[b] rows (`AttentionFn`'s variable-length form; heads of <= 128 columns)."""
     H = attn.num_attention_heads
     hd = attn.attention_head_size
     if hd > 128 and hd != 448:
@@ -218,7 +231,7 @@ def attention_block(attn, q_in, k, v, want_stats=False, patches_per_frame=196, n
                        ACT_NONE)
     # (the fused step's last formation layer carries the frame scores on the SAME schedule as every other attention of
     # the shape - round 3 - so there is no special case here: `ops.attention` takes that schedule)
-    ctxv, lse = AttentionFn.apply(q, k, v, H, scale, head_width(hd), False, nb)
+    ctxv, lse = AttentionFn.apply(q, k, v, H, scale, head_width(hd), False, nb, key_counts)
     d = attn.residual
     out = DenseResidualNormFn.apply(ctxv, pad_heads_in(d.dense.weight, H, hd).to(dt), d.dense.bias, q_in,
                                     d.layernorm.weight, d.layernorm.bias, d.layernorm.eps)

@@ -413,6 +413,129 @@ def attention_bwd_batch(q, k, v, o, do, lse2, heads, nb, need_dq=True, need_dk=T
     return dq, dk, dv
 
 
+# ---- variable-length row batches (clip batches): every video its own key count, keys packed back to back -------------------------
+def _kv_varlen(t, key_counts, what):
+    """Packed keys / values of a variable-length row batch: t [sum(key_counts), >= W] with unit inner stride (a column view of a
+    wider buffer is fine), video b's rows at prefix_b .. prefix_b + key_counts[b].  Returns (row stride, per-video element
+    offsets); refuses on the host what the C side would refuse, with a message."""
+    S = [int(s) for s in key_counts]
+    if not 1 <= len(S) <= 16 or min(S) < 1:
+        raise capi.MavlmError(f"{what}: 1..16 videos with at least one key each (got {S})")
+    if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != sum(S):
+        raise capi.MavlmError(f"{what}: expected a [sum(key_counts), W] tensor with unit inner stride")
+    ld, pre = t.stride(0), 0
+    offs = []
+    for s in S:
+        offs.append(pre * ld)
+        pre += s
+    return ld, offs
+
+
+def _i32s(v):
+    return (capi.i32 * len(v))(*[int(x) for x in v])
+
+
+def _i64s(v):
+    import ctypes
+    return (ctypes.c_int64 * len(v))(*[int(x) for x in v])
+
+
+def attention_batch_varlen(q, k, v, heads, key_counts, want_lse=False, head_dim=128, scale=None):
+    """`attention_batch` for videos of DIFFERENT key counts in ONE launch (`mavlm_attention_batch_varlen`; heads of <= 128
+    columns): q [nb*R, >=heads*128] holds the videos' query rows one after the other, k / v are [sum(key_counts), >=heads*128]
+    with video b's keys at rows prefix_b .. prefix_b + key_counts[b] (same row stride for both).  Always the plain grid: video
+    b's rows equal `attention(..., plain=True)` on its own operands bit for bit.
+    Returns (ctx [nb*R, heads*128], lse2 [nb*heads, R] fp32 | None)."""
+    _need_gpu(q, k, v)
+    nb = len(key_counts)
+    RB, _, ldq = _rows(q)
+    ldk, offs = _kv_varlen(k, key_counts, "attention_batch_varlen")
+    ldv, _ = _kv_varlen(v, key_counts, "attention_batch_varlen")
+    W = heads * 128
+    if RB % nb or ldv != ldk or q.shape[1] < W or k.shape[1] < W or v.shape[1] < W or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise capi.MavlmError("attention_batch_varlen: operand mismatch (stacked query rows, packed K / V with one row stride)")
+    R, H = RB // nb, heads * nb
+    out = torch.empty((RB, W), device=q.device, dtype=q.dtype)
+    lse = torch.empty((H, R), device=q.device, dtype=torch.float32) if want_lse else None
+    capi.check(capi.lib().mavlm_attention_batch_varlen(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(),
+                                                       out.stride(0), lse.data_ptr() if want_lse else None, R, _i32s(key_counts),
+                                                       _i64s(offs), H, 1.0 / math.sqrt(float(head_dim)) if scale is None else float(scale),
+                                                       nb, head_dim, dtype_code(q.dtype), stream_ptr()),
+               "mavlm_attention_batch_varlen")
+    return out, lse
+
+
+def attention_colsum_batch_varlen(q, k, lse2, heads, key_counts, head_dim=128, scale=None):
+    """`attention_colsum_batch` for videos of different key counts in ONE launch (`mavlm_attention_colsum_batch_varlen`): operands
+    as `attention_batch_varlen`, lse2 [nb*heads, R] as it returns it.  Every video runs the single-video schedule of its own shape:
+    bit-identical to nb `attention_colsum` calls.  Returns a list of [heads, key_counts[b]] fp32 views of the pass's plane buffer."""
+    _need_gpu(q, k, lse2)
+    nb = len(key_counts)
+    RB, _, ldq = _rows(q)
+    ldk, offs = _kv_varlen(k, key_counts, "attention_colsum_batch_varlen")
+    W = heads * 128
+    if RB % nb or q.shape[1] < W or k.shape[1] < W or k.dtype != q.dtype or lse2.dtype != torch.float32 \
+            or not lse2.is_contiguous() or lse2.numel() != nb * heads * (RB // nb):
+        raise capi.MavlmError("attention_colsum_batch_varlen: operand mismatch (stacked query rows, packed K, lse2 [nb*heads, R] fp32)")
+    R = RB // nb
+    lib = capi.lib()
+    S = _i32s(key_counts)
+    per = [int(lib.mavlm_attention_colsum_floats(R, int(s), heads)) for s in key_counts]
+    buf = torch.empty((sum(per),), device=q.device, dtype=torch.float32)
+    capi.check(lib.mavlm_attention_colsum_batch_varlen(q.data_ptr(), ldq, k.data_ptr(), ldk, _i64s(offs), lse2.data_ptr(), buf.data_ptr(),
+                                                       buf.numel(), R, S, heads, nb, head_dim,
+                                                       1.0 / math.sqrt(float(head_dim)) if scale is None else float(scale),
+                                                       dtype_code(q.dtype), stream_ptr()), "mavlm_attention_colsum_batch_varlen")
+    out, at = [], 0
+    for s, n in zip(key_counts, per):
+        out.append(buf[at:at + heads * int(s)].view(heads, int(s)))
+        at += n
+    return out
+
+
+def attention_bwd_batch_varlen(q, k, v, o, do, lse2, heads, key_counts, need_dq=True, need_dk=True, need_dv=True, scale=None,
+                               head_dim=128, dk_out=None, dv_out=None):
+    """Gradients of `attention_batch_varlen` in one launch per output (`mavlm_attention_bwd_batch_varlen`): video b's rows equal
+    `attention_bwd` on its own operands bit for bit.  Returns (dq [nb*R, W] | None, dk | None, dv | None), dk / dv
+    [sum(key_counts), W] packed as k / v; `dk_out` / `dv_out`: caller-owned packed destinations to write instead (same row stride
+    for both; rows and columns outside the videos' ranges are left untouched)."""
+    _need_gpu(q, k, v, o, do, lse2, dk_out, dv_out)
+    nb = len(key_counts)
+    RB, _, ldq = _rows(q)
+    ldk, offs = _kv_varlen(k, key_counts, "attention_bwd_batch_varlen")
+    ldv, _ = _kv_varlen(v, key_counts, "attention_bwd_batch_varlen")
+    _, _, ldo = _rows(o)
+    do = do if do.stride(-1) == 1 else do.contiguous()
+    _, _, lddo = _rows(do)
+    W = heads * 128
+    H = heads * nb
+    if RB % nb or ldv != ldk or k.shape[1] < W or v.shape[1] < W or o.shape != (RB, W) or do.shape != (RB, W) \
+            or lse2.shape != (H, RB // nb) or lse2.dtype != torch.float32 or not lse2.is_contiguous() or do.dtype != q.dtype \
+            or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise capi.MavlmError("attention_bwd_batch_varlen: operand mismatch")
+    R, tot = RB // nb, k.shape[0]
+    dq = torch.empty((RB, W), device=q.device, dtype=q.dtype) if need_dq else None
+    dk = (dk_out if dk_out is not None else torch.empty((tot, W), device=q.device, dtype=q.dtype)) if need_dk else None
+    dv = (dv_out if dv_out is not None else torch.empty((tot, W), device=q.device, dtype=q.dtype)) if need_dv else None
+    lddk = lddv = W
+    doffs = [0] * nb
+    geo = [_kv_varlen(t, key_counts, "attention_bwd_batch_varlen") for t in (dk, dv) if t is not None]
+    if geo:
+        if any(g[0] != geo[0][0] for g in geo) or any(t is not None and (t.shape[1] != W or t.dtype != q.dtype) for t in (dk, dv)):
+            raise capi.MavlmError("attention_bwd_batch_varlen: dk / dv destinations must be [sum(key_counts), W] with one row stride")
+        lddk = lddv = geo[0][0]
+        doffs = geo[0][1]
+    delta = torch.empty((H, R), device=q.device, dtype=torch.float32)
+    p = lambda t: t.data_ptr() if t is not None else 0
+    capi.check(capi.lib().mavlm_attention_bwd_batch_varlen(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo,
+                                                           do.data_ptr(), lddo, lse2.data_ptr(), delta.data_ptr(), p(dq), W, p(dk), lddk,
+                                                           p(dv), lddv, R, _i32s(key_counts), _i64s(offs), _i64s(doffs), H,
+                                                           1.0 / math.sqrt(float(head_dim)) if scale is None else float(scale),
+                                                           nb, head_dim, dtype_code(q.dtype), stream_ptr()),
+               "mavlm_attention_bwd_batch_varlen")
+    return dq, dk, dv
+
+
 def transpose(x, pad_to=64, out_rows=None):
     """[rows, cols] 16-bit -> [cols, roundup(rows, 64)] with a zero-filled pad (the K-contiguous operand form of
     the contract-over-rows products).  `out_rows` > cols: the result gets that many rows, the extra ones zero (an

@@ -36,16 +36,28 @@ struct BIC { static constexpr int value = V; };
 
 __device__ __forceinline__ int bimg_x(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
-template <typename T, int MODE>
+// Variable-length row batch (VL; MODE 0-2): video b has its own key count vl.S[b]; its keys start vl.off[b] elements into K / V
+// and its key gradients vl.doff[b] elements into dK / dV - the by-value arrays replace the keys' row count and vb * kvb /
+// vb * okvb.  The queries' side stays stacked, R rows per video.  Everything below - clamps, descriptor ends, masks, the
+// stores' bound - derives from that video's count, so video b's rows carry the bits of a single-video launch over its operands;
+// keys packed back to back are never read or written across a video's end.  The instantiations without VL take an empty argument.
+template <bool VL> struct attn_bwd_vl_arg {};
+template <> struct attn_bwd_vl_arg<true> { int S[MAVLM_VBASE_MAX]; long long off[MAVLM_VBASE_MAX]; long long doff[MAVLM_VBASE_MAX]; };
+
+__device__ __forceinline__ int vl_count(const attn_bwd_vl_arg<true>& vl, int vb) { return vl.S[vb]; }
+__device__ __forceinline__ int vl_count(const attn_bwd_vl_arg<false>&, int) { return 0; }
+
+template <typename T, int MODE, bool VL = false>
 __global__ __launch_bounds__(256, (MODE == 3 ? 1 : 2)) void attn_bwd_kernel(const uint16_t* __restrict__ X, int ldx,
                                                           const uint16_t* __restrict__ X2, int ldx2,
                                                           const uint16_t* __restrict__ Y, int ldy,
                                                           const uint16_t* __restrict__ Y2, int ldy2,
                                                           const float* __restrict__ lse2, const float* __restrict__ delta,
-                                                          uint16_t* __restrict__ Out, int ldo, int NX, int NY, int R,
+                                                          uint16_t* __restrict__ Out, int ldo, int NX_, int NY_, int R,
                                                           int H, float c, float out_scale,
                                                           uint16_t* __restrict__ Out2, int ldo2, int Hv,
-                                                          long long kvb, long long okvb) {
+                                                          long long kvb, long long okvb, attn_bwd_vl_arg<VL> vl = {}) {
+  static_assert(!VL || MODE != 3, "the variable-length form has no fused dK + dV kernel");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -53,13 +65,26 @@ __global__ __launch_bounds__(256, (MODE == 3 ? 1 : 2)) void attn_bwd_kernel(cons
   const int h = blockIdx.x % H;
   const int x0 = (blockIdx.x / H) * 128 + wave * 32;
   const int r = lane & 31, hh = lane >> 5;
-  const int nt = (NY + BKT - 1) / BKT;
   // row batch: H counts the heads of all videos, Hv per video.  Head h belongs to video vb and sits at the columns of head hc;
   // every operand moves to that video's rows - the queries' side is stacked (R rows per video), the keys' side lies kvb
   // elements apart (the key gradients okvb) - so that all row indices, the descriptors' ends and the 32-bit offsets below
   // stay those of ONE video.  (A single video: vb = 0, hc = h.)
   const int vb = h / Hv, hc = h - vb * Hv;
-  if (MODE == 0) {
+  // (VL: the launch passes the queries' R for both counts; the keys' side takes this video's)
+  const int NX = (VL && MODE != 0) ? vl_count(vl, vb) : NX_, NY = (VL && MODE == 0) ? vl_count(vl, vb) : NY_;
+  const int nt = (NY + BKT - 1) / BKT;
+  if constexpr (VL) {
+    // dK / dV: the grid covers the longest video - a workgroup past this video's last key block leaves, all four waves
+    // alike (blockIdx and vb are workgroup-uniform), before the first LDS-DMA and the first barrier
+    if (MODE != 0 && (int)(blockIdx.x / H) * 128 >= NX) return;
+    const long long kv0 = vl.off[vb], okv0 = vl.doff[vb];
+    if (MODE == 0) {
+      X += (size_t)vb * NX * ldx; X2 += (size_t)vb * NX * ldx2; Y += kv0; Y2 += kv0; Out += (size_t)vb * NX * ldo;
+    } else {
+      X += kv0; Y += (size_t)vb * NY * ldy; Y2 += (size_t)vb * NY * ldy2; Out += okv0;
+      if (MODE != 2) X2 += kv0;
+    }
+  } else if (MODE == 0) {
     X += (size_t)vb * NX * ldx; X2 += (size_t)vb * NX * ldx2; Y += vb * kvb; Y2 += vb * kvb; Out += (size_t)vb * NX * ldo;
   } else {
     X += vb * kvb; Y += (size_t)vb * NY * ldy; Y2 += (size_t)vb * NY * ldy2; Out += vb * okvb;
@@ -449,10 +474,59 @@ hipError_t launch_all(const mavlm_attn_bwd_args& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// Variable-length row batch: video b has a.vl_S[b] keys at a.vl_off[b] (K, V) and its key gradients at a.vl_doff[b] (dK, dV);
+// a.S, a.kv_bstride and a.dkv_bstride are not read.  Always MODE 0, 1 and 2 (the fused dK + dV experiment has no such form).
+// dQ runs the grid of the equal-length row batch; dK / dV run the key blocks of the LONGEST video x all heads, and the
+// workgroups past a shorter video's last block leave at once.
+template <typename T>
+hipError_t launch_all_vl(const mavlm_attn_bwd_args& a, hipStream_t s) {
+  const int nb = a.nb;
+  if (!a.vl_S || !a.vl_off || !a.vl_doff || nb < 1 || nb > MAVLM_VBASE_MAX || a.H <= 0 || a.H % nb || a.R <= 0)
+    return hipErrorInvalidValue;
+  // the 32-bit buffer offsets of launch_all (one tile past the end included), per video
+  const double lim = 2147483648.0;
+  if (((double)a.R + 64) * a.ldq * 2.0 >= lim || ((double)a.R + 64) * a.lddo * 2.0 >= lim) return hipErrorInvalidValue;
+  attn_bwd_vl_arg<true> vl = {};
+  int smax = 0;
+  for (int b = 0; b < nb; ++b) {
+    const int S = a.vl_S[b];
+    if (S < 1 || a.vl_off[b] < 0 || a.vl_doff[b] < 0 || ((double)S + 64) * a.ldk * 2.0 >= lim || ((double)S + 64) * a.ldv * 2.0 >= lim)
+      return hipErrorInvalidValue;
+    vl.S[b] = S; vl.off[b] = a.vl_off[b]; vl.doff[b] = a.vl_doff[b];
+    smax = S > smax ? S : smax;
+  }
+  const float c = a.scale * 1.44269504088896340736f;
+  static mavlm_per_device_once once[3];
+  {
+    hipError_t e = once[0].dyn_lds((const void*)attn_bwd_kernel<T, 0, true>, BWD_LDS);
+    if (e == hipSuccess) e = once[1].dyn_lds((const void*)attn_bwd_kernel<T, 1, true>, BWD_LDS);
+    if (e == hipSuccess) e = once[2].dyn_lds((const void*)attn_bwd_kernel<T, 2, true>, BWD_LDS);
+    if (e != hipSuccess) return e;
+  }
+  const int Hv = a.H / nb;
+  hipLaunchKernelGGL(attn_delta_kernel<T>, dim3((nb * a.R + 3) / 4), dim3(256), 0, s, (const uint16_t*)a.O, a.ldo,
+                     (const uint16_t*)a.dO, a.lddo, a.delta, a.R, Hv, nb);
+  const dim3 gq(((a.R + 127) / 128) * a.H), gk(((smax + 127) / 128) * a.H);
+  auto launch = [&](auto kern, dim3 grid, const void* X, int ldx, const void* X2, int ldx2, const void* Y, int ldy, const void* Y2,
+                    int ldy2, void* out, int ldo, float out_scale) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), BWD_LDS, s, (const uint16_t*)X, ldx, (const uint16_t*)X2, ldx2, (const uint16_t*)Y,
+                       ldy, (const uint16_t*)Y2, ldy2, a.lse2, a.delta, (uint16_t*)out, ldo, a.R, a.R, a.R, a.H, c, out_scale,
+                       (uint16_t*)nullptr, 0, Hv, 0ll, 0ll, vl);
+  };
+  if (a.dQ != nullptr) launch(attn_bwd_kernel<T, 0, true>, gq, a.Q, a.ldq, a.dO, a.lddo, a.K, a.ldk, a.V, a.ldv, a.dQ, a.lddq, a.scale);
+  if (a.dK != nullptr) launch(attn_bwd_kernel<T, 1, true>, gk, a.K, a.ldk, a.V, a.ldv, a.Q, a.ldq, a.dO, a.lddo, a.dK, a.lddk, a.scale);
+  if (a.dV != nullptr) launch(attn_bwd_kernel<T, 2, true>, gk, a.K, a.ldk, nullptr, 0, a.Q, a.ldq, a.dO, a.lddo, a.dV, a.lddv, 1.0f);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 int g_mavlm_attn_bwd_fused = 0;   // experiment switch: 1 = fused dK+dV kernel (512-register waves, one workgroup per CU)
 
 hipError_t mavlm_launch_attention_bwd(const mavlm_attn_bwd_args& a, int dtype, hipStream_t s) {
   return dtype == MAVLM_F16 ? launch_all<F16>(a, s) : launch_all<BF16>(a, s);
+}
+
+hipError_t mavlm_launch_attention_bwd_varlen(const mavlm_attn_bwd_args& a, int dtype, hipStream_t s) {
+  return dtype == MAVLM_F16 ? launch_all_vl<F16>(a, s) : launch_all_vl<BF16>(a, s);
 }

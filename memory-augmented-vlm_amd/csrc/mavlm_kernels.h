@@ -193,8 +193,16 @@ struct mavlm_attn_bwd_args {
   // keeps one owner: a batched launch gives the bits of nb single launches.  nb = 1: a single video.
   int nb = 1;
   long long kv_bstride = 0, dkv_bstride = 0;
+  // variable-length row batch (mavlm_launch_attention_bwd_varlen only): HOST arrays of nb <= MAVLM_VBASE_MAX entries - video b has
+  // vl_S[b] keys that start vl_off[b] elements into K and V, its key gradients vl_doff[b] elements into dK and dV; S and the two
+  // strides are not read
+  const int* vl_S = nullptr;
+  const long long* vl_off = nullptr;
+  const long long* vl_doff = nullptr;
 };
 hipError_t mavlm_launch_attention_bwd(const mavlm_attn_bwd_args& a, int dtype, hipStream_t s);
+// per-video key counts (attention_bwd.hip): video b's rows of dQ / dK / dV carry the bits of a single launch over its operands
+hipError_t mavlm_launch_attention_bwd_varlen(const mavlm_attn_bwd_args& a, int dtype, hipStream_t s);
 extern int g_mavlm_attn_bwd_fused;      // attention_bwd.hip (mavlm_set_attention_bwd_fused)
 // the same for head_dim 448 (attention_bwd_hd.hip); O / dO / dQ / dK / dV are [rows, H*448]
 hipError_t mavlm_launch_attention_bwd_hd(const mavlm_attn_bwd_args& a, int head_dim, int dtype, hipStream_t s);

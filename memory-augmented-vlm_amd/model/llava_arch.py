@@ -283,7 +283,7 @@ def _memory_rows(mp_rows, n, R, layout, P):
     return mp_rows, mp_rows + (layout_block_rows(n * R, layout, P) if layout_period(layout, P) else n * R)
 
 
-def _prepare_row_batch(kind, name, model, bp, images, frame_idx_cpu, chunk, fine_frames):
+def _prepare_row_batch(kind, name, model, bp, images, frame_idx_cpu, chunk, fine_frames, emit=True):
     """What every row-batch driver does before the first step.  `kind`: "equal" (bp.batch videos of one length), "ragged"
     (2 .. bp.batch videos, each a positive multiple of `chunk` frames, the same number of fine frames) or "clips" (2 .. bp.batch
     videos of 1 .. chunk - 1 frames); `name`: the public function the caller called, for the error texts.  Validates the images
@@ -292,7 +292,9 @@ def _prepare_row_batch(kind, name, model, bp, images, frame_idx_cpu, chunk, fine
     original indices), orders the videos longest first (stable: the caller's order for equal lengths), adds the positional
     encoding per video (llava_arch.py:510-511; consecutive videos with the same index tensor share its check and device copy)
     and computes the fine-frame indices (:513-522).  Returns (xs, fines, order, back) - PE-added frames and fine indices in the
-    stepping order, `order[j]` = the caller's position of the j-th video stepped, `back` its inverse."""
+    stepping order, `order[j]` = the caller's position of the j-th video stepped, `back` its inverse.  `emit` False: the caller
+    builds the blocks from torch ops and the plain GEMMs (the training tail), so the hidden-size rule of the clip emit does not
+    apply."""
     k = len(images)
     if (k != bp.batch) if kind == "equal" else (not 2 <= k <= bp.batch):
         raise capi.MavlmError(f"{name}: {bp.batch if kind == 'equal' else f'2..{bp.batch}'} videos expected")
@@ -315,7 +317,7 @@ def _prepare_row_batch(kind, name, model, bp, images, frame_idx_cpu, chunk, fine
         idxs = [frame_idx_cpu] * k if kind == "equal" else []
     if len(idxs) != k or any(i.numel() != im.shape[0] for i, im in zip(idxs, images)):
         raise capi.MavlmError(f"{name}: one frame index tensor per video, of its length")
-    if kind == "clips" and D % 256:                  # (refused before any step: mavlm_fuse_emit_layout_frames_to would, afterwards)
+    if kind == "clips" and emit and D % 256:         # (refused before any step: mavlm_fuse_emit_layout_frames_to would, afterwards)
         raise capi.MavlmError(f"{name}: the clip emit needs a hidden size that is a multiple of 256; got {D}")
     pe: TemporalPositionalEncoding = model.positional_encoding
     order = sorted(range(k), key=lambda i: -images[i].shape[0])            # longest first; stable in the caller's order
@@ -522,6 +524,34 @@ def video_memory_tokens_batched_train(model, bp: BatchedProjector, images, frame
     nl, mp, fp = _train_tail_operands(image_newline, memory_prompt_embeds, frame_prompt_embeds, layout, xs[0])
     toks = [_train_block(model, fused[:, b].reshape(n * R, D), xs[b], fines[b], mp, fp, nl, with_frames, layout) for b in range(B)]
     return torch.stack(toks), _row_batch_info("equal", bp, xs, fines, [n] * B, None, order, back, mp.shape[0], layout)
+
+
+def video_memory_tokens_clips_train(model, bp: BatchedProjector, images, frame_idx_cpu, memory_prompt_embeds: torch.Tensor,
+                                    frame_prompt_embeds: torch.Tensor, image_newline: Optional[torch.Tensor],
+                                    with_frames: bool = True, chunk: int = 32, fine_frames: int = 32, layout: str = "one_token"):
+    """`video_memory_tokens_clips` under autograd: k clips (2 <= k <= bp.batch) of 1 <= T_b < `chunk` frames each, ordered
+    longest first (stable), take ONE step together - `BatchedProjector.step_train_frames`: the variable-length attention forward
+    and backward over the packed chunk K/V - then the fuser runs over the k * R stacked memory rows in one GEMM pair and
+    `_train_block` builds every video's block (every frame of a clip is a fine frame).  Where that GEMM pair does not split its
+    contraction the feature rows are the bits of the inference clip block.  The block is built from torch ops and the plain
+    GEMMs: every hidden size the training path takes, 896 included (the inference clip emit needs a multiple of 256).  Heads of
+    448 columns have no variable-length attention: clips of different lengths are refused at that width
+    (`step_train_frames`).  Returns (list of [rows_b, D] blocks with grad in the caller's order, info as
+    `video_memory_tokens_clips`)."""
+    from .. import _autograd as ag
+    layout_period(layout, images[0].shape[1])
+    xs, fines, order, back = _prepare_row_batch("clips", "video_memory_tokens_clips_train", model, bp, images, frame_idx_cpu, chunk,
+                                                fine_frames, emit=False)
+    k = len(xs)
+    bp.reset()                                                                             # :532
+    bp.step_train_frames(xs)                                                               # :534-537: one chunk each
+    P, D = xs[0].shape[1:]
+    R = bp.proj.num_memory_tokens * P
+    fused = ag.fuser_mlp(model.memory_fuser, bp._tcache[-1], model.token_type_embedding.weight[0], fused_gelu=True)   # :545-553
+    nl, mp, fp = _train_tail_operands(image_newline, memory_prompt_embeds, frame_prompt_embeds, layout, xs[0])
+    toks = [_train_block(model, fused[b * R:(b + 1) * R], xs[b], fines[b], mp, fp, nl, with_frames, layout) for b in range(k)]
+    info = _row_batch_info("clips", bp, xs, fines, [1] * k, [t.shape[0] for t in toks], order, back, mp.shape[0], layout)
+    return [toks[j] for j in back], info
 
 
 def _ragged_fuser_rows(lib, counts, R, D, inter):
@@ -800,9 +830,15 @@ def features_per_sample(video_of, tokens):
     return [tokens[v] if v >= 0 else None for v in video_of]
 
 
+def _narrow_heads(rm) -> bool:
+    """heads of at most 128 columns - the widths the variable-length attention serves (a model without layers: nothing to ask)"""
+    layers = getattr(rm, "layers", None)
+    return not layers or layers[0].memory_segment_fusion_attention.attention_head_size <= 128
+
+
 def run_video_groups(model, videos, mem_prompt, frame_prompt, image_newline, with_frames=True, layout="one_token",
                      sizes=ROW_BATCH_SIZES, train=False, out=None, dst_rows=None, single=None, ragged=False, ragged_train=False,
-                     clips=False):
+                     clips=False, clips_train=False):
     """The memory path for several videos on the current stream - the ONE place that groups videos into row batches.
     `videos`: (pooled frame tokens [T, P, D], original frame indices [T] on the host) per video.  Videos with the same sampled
     frame count, dtype and device form a group (they share chunk bounds and fine-frame indices); `plan_row_batches` cuts it into
@@ -820,13 +856,23 @@ def run_video_groups(model, videos, mem_prompt, frame_prompt, image_newline, wit
     changes nothing.
     `clips` (LlavaMetaForCausalLM.enable_clip_row_batches; inference - under autograd it changes nothing): the videos of fewer
     than 32 sampled frames are grouped by `plan_clip_batches` first - different frame counts in ONE step, one emit per group
-    (`video_memory_tokens_clips`); every other video goes through the grouping above."""
+    (`video_memory_tokens_clips`); every other video goes through the grouping above.
+    `clips_train` (enable_clip_row_batches(on, training=True)): with `train` the clips are grouped by `plan_clip_batches` too
+    and a group runs through `video_memory_tokens_clips_train`; without `train` it changes nothing.  Heads of 448 columns
+    have no variable-length attention: at that width it changes nothing either - the grouping stays as it is today."""
     rm = model.recurrent_memory_transformer
-    if clips and not train:
+    if (clips and not train) or (clips_train and train and _narrow_heads(rm)):
         cgroups, rest = plan_clip_batches([v[0].shape[0] for v in videos], [(v[0].dtype, str(v[0].device)) for v in videos], sizes)
         if cgroups:
             tokens = [None] * len(videos)
             for size, grp in cgroups:
+                if train:
+                    toks = video_memory_tokens_clips_train(model, rm.row_batcher(size), [videos[i][0] for i in grp],
+                                                           [videos[i][1] for i in grp], mem_prompt, frame_prompt, image_newline,
+                                                           with_frames, layout=layout)[0]
+                    for j, i in enumerate(grp):
+                        tokens[i] = toks[j]
+                    continue
                 toks = video_memory_tokens_clips(model, rm.row_batcher(size), [videos[i][0] for i in grp], [videos[i][1] for i in grp],
                                                  mem_prompt, frame_prompt, image_newline, with_frames, out=out, layout=layout,
                                                  dst_rows=None if out is None else [dst_rows[i] for i in grp])[0]
@@ -1304,7 +1350,8 @@ class LlavaMetaForCausalLM:
             tokens = run_video_groups(model, vids, mem_prompt, frame_prompt, newline, not drop, layout, self.row_batch_sizes,
                                       train=train, ragged=self._ragged_row_batches and not train,
                                       ragged_train=self._ragged_row_batches_train and train,
-                                      clips=self._clip_row_batches and not train)
+                                      clips=self._clip_row_batches and not train,
+                                      clips_train=self._clip_row_batches_train and train)
             return splice_into_text(self, model, features_per_sample(plan.video_of, tokens), input_ids, position_ids,
                                     attention_mask, past_key_values, labels)
         # in place: the padded buffer once, text rows from embed_tokens, padding zeroed, every block emitted where it belongs
@@ -1345,18 +1392,25 @@ class LlavaMetaForCausalLM:
         self._ragged_row_batches_train = bool(on) and bool(training)
 
     _clip_row_batches = False
+    _clip_row_batches_train = False
 
-    def enable_clip_row_batches(self, on: bool = True):
+    def enable_clip_row_batches(self, on: bool = True, training: bool = False):
         """Several videos per forward: let the videos of FEWER than 32 frames share a row batch (off by default).  Such a video
         is one chunk of all its frames, so two of them step together only when their frame counts are equal; everything else
         runs as single videos.  On, they are grouped by `plan_clip_batches`: up to 8 clips whose lengths differ by at most a
         factor of two share one row-batched engine and take ONE step with a frame count per video (`mavlm_step_batch_frames`),
-        then one emit per group into the padded `inputs_embeds`.  Inference only: a forward that records a graph keeps the
+        then one emit per group into the padded `inputs_embeds`.  Inference; a forward that records a graph keeps the
         grouping of the switch off.  Independent of `enable_ragged_row_batches` (which serves the videos of 32 frames and more).
         The other row-batched emits take every hidden size that is a multiple of 128; the clip emit (a fine-frame count per
         video, `mavlm_fuse_emit_layout_frames_to`) still needs a multiple of 256 (D = 896: `MavlmError` before any step).
-        Measured 1.23 x at D = 1024 and 0.96 x (slower) at D = 3584 with 4 clips: hence off by default."""
+        Measured 1.23 x at D = 1024 and 0.96 x (slower) at D = 3584 with 4 clips: hence off by default.
+        `training=True` additionally groups the clips of a forward under autograd that way (off by default, also with `on`): a
+        group takes one `BatchedProjector.step_train_frames` - the variable-length attention forward and backward - and
+        `video_memory_tokens_clips_train` builds its blocks, at every hidden size of the training path (896 included).  Heads
+        of 448 columns have no variable-length attention: at that width the training grouping stays as it is with the switch
+        off.  `on=False` switches both off."""
         self._clip_row_batches = bool(on)
+        self._clip_row_batches_train = bool(on) and bool(training)
 
     # -- hipGraph replay for repeated video shapes (round 4) -------------------------------------------------------------
     def enable_memory_graphs(self, capacity: int = 4):

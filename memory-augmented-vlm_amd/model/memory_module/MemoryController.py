@@ -699,14 +699,16 @@ class TransformerProjector(nn.Module):
         return self._memory_cache, self.frame_attn_scores
 
 
-def _form_memory(ag, proj, m, kvs, want_stats, P, nb=1):
+def _form_memory(ag, proj, m, kvs, want_stats, P, nb=1, key_counts=None):
     """Memory formation of the training paths (:132-133): the layers of `proj` over the memory rows `m` ([nb * R, D], the stacked
     rows of nb videos) and the chunk's projected K/V `kvs` (one pair per layer).  Returns (new memory rows, the (q, k, lse2) of
-    the last layer's attention for the frame scores - None without `want_stats`)."""
+    the last layer's attention for the frame scores - None without `want_stats`).  `key_counts`: the videos' chunks differ in
+    length - `kvs` are packed [sum(key_counts), W] pairs and every layer runs the variable-length attention."""
     stats = None
     for li, layer in enumerate(proj.layers):
         a, stats = ag.attention_block(layer.memory_segment_fusion_attention, m, kvs[li][0], kvs[li][1],
-                                      want_stats=want_stats and li == len(proj.layers) - 1, patches_per_frame=P, nb=nb)
+                                      want_stats=want_stats and li == len(proj.layers) - 1, patches_per_frame=P, nb=nb,
+                                      key_counts=key_counts)
         m = ag.mlp_block(layer, a)
     return m, stats
 
@@ -772,7 +774,9 @@ class BatchedProjector:
     `BatchedProjector` of size k; k = 1: those of the single-video training step), and the frame scores of all k videos come from
     ONE column-sum launch (`ops.attention_colsum_batch`).  The FIFO is per video (`ragged_fifo_plan`): a finished video keeps the
     memories of its own last steps until `reset()`.  A batch is ragged or not from its first step on; the step without the
-    keyword is the same body at k = B."""
+    keyword is the same body at k = B.  `step_train_frames(segs)` is that ragged step for chunks of DIFFERENT frame counts (clips
+    of fewer than 32 frames) - `step_frames` under autograd: the variable-length attention forward and backward over the packed
+    chunk K/V (heads of at most 128 columns)."""
 
     def __init__(self, proj: TransformerProjector, batch: int, fused_ln_never: bool = False):
         self.fused_ln_never = bool(fused_ln_never)
@@ -919,6 +923,21 @@ class BatchedProjector:
         1 .. the count of the step before; returns [len(segs), F] scores.  One body serves both: the equal-length step is the
         ragged step over k = B videos.  Rows [:k*R] of the newest cached memory and [:k] of the cached evolution K/V are the active
         videos'; a cached memory is projected for the evolution over the rows of the videos that step again only."""
+        return self._step_train("step_train", segs, ragged, False)
+
+    def step_train_frames(self, segs):
+        """`step_train(ragged=True)` for chunks that differ in their FIRST dimension: segs = k tensors [F_b, P, D], the clips of
+        fewer than 32 frames whose single chunk holds all their frames - `step_frames` under autograd, with its prefix rule.  The
+        evolution and the FIFO are `step_train`'s own (they do not depend on F); the chunk K/V of all videos are packed back to
+        back, every formation layer runs the variable-length attention, forward (`ops.attention_batch_varlen`) and backward
+        (`ops.attention_bwd_batch_varlen`), and the frame scores come from ONE variable-length column-sum launch.  Returns a list
+        of k detached [F_b] frame scores (None with `compute_frame_scores = False`); `frame_scores` gets one padded [k, Fmax]
+        tensor (zeros behind a video's F_b).  Equal F_b take the launches and the bits of `step_train(ragged=True)`.  Heads of 448
+        columns have no variable-length kernel: different F_b at that width are refused before any launch.  No attention maps."""
+        return self._step_train("step_train_frames", segs, True, True)
+
+    def _step_train(self, name, segs, ragged, frames):
+        """the body of `step_train` (`frames` False: chunks of one shape) and of `step_train_frames` (`frames` True)"""
         from ... import _autograd as ag
         proj, B = self.proj, self.batch
         k = len(segs)
@@ -926,11 +945,17 @@ class BatchedProjector:
             raise capi.MavlmError("record_attention_maps is not supported on the autograd (training) path: attention maps are "
                                   "recorded by inference steps only")
         if ragged:
-            self._check_train_mode(True)
-            self._check_prefix("step_train(ragged=True)", k)
+            self._check_train_mode(True, name)
+            self._check_prefix(name if frames else "step_train(ragged=True)", k)
         elif k != B:
             raise capi.MavlmError(f"BatchedProjector.step_train: {B} chunks expected")
-        F = self._check_chunks("step_train", segs, True, contiguous=False)[0]
+        if frames and len({int(t.shape[0]) for t in segs if t.dim() == 3}) > 1 \
+                and proj.layers[0].memory_segment_fusion_attention.attention_head_size > 128:
+            raise capi.MavlmError("BatchedProjector.step_train_frames: chunks of different frame counts need the variable-length "
+                                  "attention, which heads of more than 128 columns (448) do not have")
+        Fs = self._check_chunks(name, segs, not frames, contiguous=False)
+        F = Fs[0]
+        varlen = len(set(Fs)) > 1                                   # else: the equal-length body, launch for launch
         if not ragged:
             self._check_train_mode(False)
         self._mode, self._tragged = "autograd", bool(ragged)
@@ -960,16 +985,27 @@ class BatchedProjector:
             self._tevo, self._tevo_steps = [], []
             m = (proj.initial_memory + proj.memory_pos_embed).to(dt).reshape(R, D).repeat(k, 1)      # :123-124, every video
         atts = [layer.memory_segment_fusion_attention for layer in proj.layers]
-        m, stats = _form_memory(ag, proj, m, self._chunk_kv(ag, atts, segs, F * P, D, k), self.compute_frame_scores, P, nb=k)
+        if varlen:
+            Sc = tuple(f * P for f in Fs)
+            m, stats = _form_memory(ag, proj, m, self._chunk_kv_packed(ag, atts, segs, Sc, D), self.compute_frame_scores, P, nb=k,
+                                    key_counts=Sc)
+        else:
+            m, stats = _form_memory(ag, proj, m, self._chunk_kv(ag, atts, segs, F * P, D, k), self.compute_frame_scores, P, nb=k)
         scores = None
         if stats is not None:                                       # :135-139, 156 (detached statistics)
             with torch.no_grad():                                   # one column-sum launch for all k videos
                 q, kl, lse = stats
                 H, hd = atts[-1].num_attention_heads, atts[-1].attention_head_size
-                part = ops.attention_colsum_batch(q, kl if k > 1 else kl.unsqueeze(0), lse, H, k, head_dim=128 if hd <= 128 else hd,
-                                                  scale=ops.attn_scale(hd))
-                # (finished per video with the single-video path's torch ops on its [H, S] plane: the same bits)
-                scores = torch.stack([_frame_scores(part[b], F, P, dt) for b in range(k)])
+                if varlen:
+                    part = ops.attention_colsum_batch_varlen(q, kl, lse, H, Sc, scale=ops.attn_scale(hd))
+                    scores = torch.zeros((k, max(Fs)), device=q.device, dtype=dt)
+                    for b in range(k):
+                        scores[b, :Fs[b]] = _frame_scores(part[b], Fs[b], P, dt)
+                else:
+                    part = ops.attention_colsum_batch(q, kl if k > 1 else kl.unsqueeze(0), lse, H, k, head_dim=128 if hd <= 128 else hd,
+                                                      scale=ops.attn_scale(hd))
+                    # (finished per video with the single-video path's torch ops on its [H, S] plane: the same bits)
+                    scores = torch.stack([_frame_scores(part[b], F, P, dt) for b in range(k)])
         self._tcache.append(m)                                      # :152
         self._tsteps.append(n)
         self._end_step(k, scores)
@@ -981,15 +1017,17 @@ class BatchedProjector:
             self._tcache, self._tsteps = [self._tcache[i] for i in keep], [self._tsteps[i] for i in keep]
         while self._tevo_steps and self._tevo_steps[0] <= self._n - cap - 1:
             self._tevo, self._tevo_steps = self._tevo[1:], self._tevo_steps[1:]
+        if frames and scores is not None:
+            return [scores[b, :Fs[b]] for b in range(k)]
         return scores
 
-    def _check_train_mode(self, ragged):
+    def _check_train_mode(self, ragged, name="step_train"):
         """a video batch runs in one mode, and under autograd ragged or not, from its first step to `reset()`"""
         if self._mode == "engine":
-            raise capi.MavlmError("BatchedProjector.step_train: this video batch was started by the inference `step`: `reset()` "
+            raise capi.MavlmError(f"BatchedProjector.{name}: this video batch was started by the inference `step`: `reset()` "
                                   "before running the training path")
         if self._tragged is not None and self._tragged != bool(ragged):
-            raise capi.MavlmError(f"BatchedProjector.step_train: this video batch was started {'with' if self._tragged else 'without'} "
+            raise capi.MavlmError(f"BatchedProjector.{name}: this video batch was started {'with' if self._tragged else 'without'} "
                                   f"`ragged=True`: `reset()` before stepping it {'with' if ragged else 'without'} the keyword")
 
     def _chunk_kv(self, ag, atts, segs, S, D, B):
@@ -1007,6 +1045,19 @@ class BatchedProjector:
             return ag.project_kv(atts, torch.cat(frames, dim=0), nb=B)
         per = [ag.project_kv(atts, f) for f in frames]
         return [(torch.stack([p[i][0] for p in per]), torch.stack([p[i][1] for p in per])) for i in range(len(atts))]
+
+    def _chunk_kv_packed(self, ag, atts, segs, Sc, D):
+        """K/V of chunks of DIFFERENT lengths (Sc[b] rows of video b) for all layers, packed back to back: [sum(Sc), W] pairs with
+        one row stride.  `_chunk_kv`'s rule: ONE GEMM over the concatenated frames where neither a video's own row count nor the
+        sum splits the contraction, else one GEMM per video, concatenated."""
+        frames = [t.detach().reshape(s, D) for t, s in zip(segs, Sc)]           # frame features carry no gradient
+        a0 = atts[0]
+        N = 2 * len(atts) * a0.num_attention_heads * ag.head_width(a0.attention_head_size)
+        lib = capi.lib()
+        if all(lib.mavlm_linear_ws_floats(s, N, D, capi.EPI_BIAS, N) == 0 for s in tuple(Sc) + (sum(Sc),)):
+            return ag.project_kv(atts, torch.cat(frames, dim=0))
+        per = [ag.project_kv(atts, f) for f in frames]
+        return [(torch.cat([p[i][0] for p in per]), torch.cat([p[i][1] for p in per])) for i in range(len(atts))]
 
     def memory_cache(self, b: int) -> List[torch.Tensor]:
         """video b's FIFO, oldest first: ring views after `step` (as TransformerProjector.memory_cache), graph-carrying

@@ -7,7 +7,12 @@ interleaved round by round in this one process; ms per step and per video, then 
 CHUNKS=3,2,2,1: videos of that many 32-frame chunks each, timed three ways, interleaved round by round in this one process: as ONE
 ragged row batch (step_train(ragged=True) on the smallest engine of 2 / 4 / 8 that holds them), under the equal-length grouping
 (plan_row_batches over the chunk counts: row batches of equal length plus single videos) and as single videos; ms per pass and per
-(video, chunk) step, then the kernel table - launches per pass - of each."""
+(video, chunk) step, then the kernel table - launches per pass - of each.
+CLIPS=31,27,23,19,16,12,9,5: clips of that many frames each (one chunk of all its frames), timed three ways, interleaved round by
+round in this one process after warming up all three: as clip row batches (plan_clip_batches; a group takes ONE
+step_train_frames - the variable-length attention forward and backward -, what is left runs under the equal-length grouping),
+under the equal-length grouping alone (plan_row_batches over the frame counts: the switch off) and as single videos; ms per pass
+and per video, then the kernel table - launches per pass - of each (ROUNDS, default 5 here)."""
 import ctypes, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -56,6 +61,75 @@ def kernel_table(fn):
                   + (f"  {fl[i]/(ms[i]*1e-3)/1e12:7.1f} TF" if fl[i] else f"  {by[i]/(ms[i]*1e-3)/1e9:7.1f} GB/s"))
     print(f"sum of HIP kernels {tot/steps:.2f} ms/step (torch glue kernels not included)")
     return tot / steps
+
+if os.environ.get("CLIPS"):
+    from memory_augmented_vlm_amd.model import llava_arch as arch
+    from memory_augmented_vlm_amd.model.memory_module.MemoryController import BatchedProjector
+    frames = [int(v) for v in os.environ["CLIPS"].split(",")]
+    vids = [(torch.randn(f, 196, HID, device="cuda") * 0.5).bfloat16() for f in frames]        # distinct clips
+    loss_of = lambda mems: sum(cm.float().square().mean() for cm in mems)
+    def single_video(v):
+        rm.memory_cache = []
+        cache, _ = rm(v)
+        return loss_of(cache)
+    def singles():
+        rm.zero_grad(set_to_none=True)
+        sum(single_video(v) for v in vids).backward()
+    bps = {}
+    def engine(size):
+        if size not in bps:
+            bps[size] = BatchedProjector(rm, size)
+        return bps[size]
+    def equal_groups(idx):
+        """the switch-off grouping of the clips `idx`: row batches of equal frame counts, the rest single videos"""
+        batches, alone = arch.plan_row_batches([frames[i] for i in idx])
+        loss = 0.0
+        for g in batches:
+            bp = engine(len(g))
+            bp.reset()
+            bp.step_train([vids[idx[j]] for j in g])
+            loss = loss + sum(loss_of(bp.memory_cache(b)) for b in range(len(g)))
+        for j in alone:
+            loss = loss + single_video(vids[idx[j]])
+        return loss
+    def grouped():
+        rm.zero_grad(set_to_none=True)
+        equal_groups(list(range(len(frames)))).backward()
+    cgroups, rest = arch.plan_clip_batches(frames)
+    def clips():
+        rm.zero_grad(set_to_none=True)
+        loss = 0.0
+        for size, g in cgroups:
+            bp = engine(size)
+            bp.reset()
+            bp.step_train_frames([vids[i] for i in g])
+            loss = loss + sum(loss_of(bp.memory_cache(b)) for b in range(len(g)))
+        if rest:
+            loss = loss + equal_groups(rest)
+        loss.backward()
+    fns = {"clips": clips, "grouped": grouped, "singles": singles}
+    eq_b, eq_a = arch.plan_row_batches(frames)
+    print(f"CLIPS={frames}  M={M} hidden={HID}; clip row batches {[[frames[i] for i in g] for _, g in cgroups]} on engines of "
+          f"{[sz for sz, _ in cgroups]}, the rest {[frames[i] for i in rest]}; equal-length grouping (the switch off): row batches "
+          f"{[[frames[j] for j in g] for g in eq_b]}, single videos {[frames[j] for j in eq_a]}")
+    for fn in fns.values():
+        for _ in range(2): fn()
+    times = {k: [] for k in fns}
+    for _ in range(int(os.environ.get("ROUNDS", "5"))):
+        for k, fn in fns.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(steps): fn()
+            torch.cuda.synchronize(); times[k].append((time.perf_counter() - t0) / steps)
+    for k in fns:
+        t = sorted(times[k])
+        print(f"{k:8s}: fwd+bwd of all clips median {t[len(t)//2]*1e3:.2f} ms  min {t[0]*1e3:.2f}  max {t[-1]*1e3:.2f}   "
+              f"per video {t[len(t)//2]*1e3/len(frames):.2f} ms   (rounds {['%.2f' % (v*1e3) for v in times[k]]})")
+    print(f"peak mem {torch.cuda.max_memory_allocated()/2**30:.2f} GiB")
+    if os.environ.get("TABLES", "1") != "0":
+        for k, fn in fns.items():
+            print(f"---- kernel kinds, {k} (per pass over all {len(frames)} clips)")
+            kernel_table(fn)
+    sys.exit(0)
 
 if os.environ.get("CHUNKS"):
     from memory_augmented_vlm_amd.model import llava_arch as arch
