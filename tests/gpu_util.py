@@ -1,4 +1,6 @@
 """Helpers shared by the -m gpu tests: numpy <-> device tensors on the 16-bit grids, oracle weights -> module."""
+import math
+
 import numpy as np
 import torch
 
@@ -188,4 +190,133 @@ def f32_sum_gate(name, got, ref, fp32_result, cols):
     ratio = e / fl.clamp_min(1e-300)
     i = int(torch.argmax(ratio))
     return Gate(name, float(ratio.view(-1)[i]), (0, i), rel_l2_t(got, ref.view(-1)) / max(float(fl.max()), 1e-300),
+                float(fl.max()), F32_SUM_BLOCK, None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Probability masses: the kernels that SUM softmax probabilities (column sums, frame scores, attention maps) compute in fp32
+# throughout, so their floor is an fp32 one, per block of the last dimension.  A query row counted twice or not at all moves a
+# block by 1 / R of its value: ~1e-4 at R = 12 544, far under a whole-tensor 1e-3, hundreds of times a block's fp32 floor.
+MASS_MIN_TAIL = 8            # a ragged last block of fewer entries is merged into the block before it
+F32_ROUND = 2.0 ** -24       # largest relative error of one correct fp32 rounding
+
+
+def attn_c32(scale):
+    """scale x log2 e as the launchers compute it (`a.scale * 1.44269504088896340736f`, one fp32 product): the constant inside the
+    kernels' exp2, exactly, as a Python float"""
+    return float(np.float32(scale) * np.float32(1.44269504088896340736))
+
+
+def lse2_offsets(heads, rows):
+    """hashed per-(head, row) offsets in [-3, 3], multiples of 1/8 (exactly representable): added to an lse2 that is handed to a
+    stand-alone pass, they give every row its own weight, so that a row read at another row's index cannot cancel"""
+    i = torch.arange(heads * rows, dtype=torch.int64)
+    return ((((i * 2654435761) >> 7) % 49 - 24).to(torch.float32) / 8.0).view(heads, rows)
+
+
+def _ulp32(x):
+    """spacing of fp32 at |x| (float64 tensor)"""
+    return torch.exp2(torch.floor(torch.log2(x.abs().clamp_min(2.0 ** -126))) - 23)
+
+
+def _f32(x):
+    """float64 -> fp32 (to nearest even) -> float64"""
+    return x.to(torch.float32).double()
+
+
+def prob_mass_eval(q, k, lse2, heads, head_dim, c, dtype=torch.float64, q_group=None, k_group=None, rows=2048, rounding=None,
+                   adds=8):
+    """The contract of the probability-mass kernels, evaluated plainly in `dtype` (float64: the reference; float32: the floor):
+    p[h][r][s] = exp2(q_h[r] . k_h[s] * c - lse2[h][r]) with the fp32 `lse2` [H, R] and the fp32 constant `c` (scale x log2 e)
+    that the kernel was handed, summed over the queries -> [H, S], or, with groups, over `q_group` consecutive rows and
+    `k_group` consecutive keys -> [H, ceil(R / q_group), ceil(S / k_group)].  Query-blocked; works on the operands' device.
+
+    `rounding` (float64 only) takes the fp32 rounding points the kernels document - the MFMA accumulator after each 16-column
+    step, the product s c, the exponent s c - lse2, the result of exp2, the additions of the sum:
+      "emulate"   rounds to nearest at each of them, the sums added in fp32: one realisation of the error, as
+                  `attention_bwd_ref64`'s `rounded` (measured on planted rows at 448 columns: the kernels' logits sit within
+                  1 .. 4 ulp of float64, either sign, like this emulation's);
+      "expected"  returns the reference plus the root-mean-square error those roundings give per output: independent errors,
+                  uniform within half an ulp at each point, `adds` additions of the sum.  Its block rel-L2 is the EXPECTED
+                  error of a block instead of one draw: the floor of blocks that hold a single exponent (a map cell of one
+                  query row, the block of a planted key), where the error of one evaluation says nothing about another's."""
+    R, S = q.shape[0], k.shape[0]
+    if q_group:
+        rows = max(q_group, rows // q_group * q_group)
+    ln2 = math.log(2.0)
+
+    def grouped(x, f32_sum=False):
+        if f32_sum:
+            x = x.to(torch.float32)
+        if not q_group:
+            return x.sum(0).double() if f32_sum else x.sum(0)
+        n, nk = x.shape[0], -(-S // k_group)
+        x = torch.nn.functional.pad(x, (0, nk * k_group - S, 0, -(-n // q_group) * q_group - n))
+        x = x.view(-1, q_group, nk, k_group).sum(dim=(1, 3))
+        return x.double() if f32_sum else x
+    out = []
+    for h in range(heads):
+        sl = slice(h * head_dim, (h + 1) * head_dim)
+        kh = k[:, sl].to(dtype)
+        acc, var = [], []
+        for r0 in range(0, R, rows):
+            qb = q[r0:r0 + rows, sl].to(dtype)
+            l = lse2[h, r0:r0 + rows, None].to(dtype)
+            if rounding is None:
+                acc.append(grouped(torch.exp2((qb @ kh.T) * c - l)))
+                continue
+            s = torch.zeros((qb.shape[0], S), device=q.device, dtype=torch.float64)
+            vs = torch.zeros_like(s)
+            for j in range(0, head_dim, 16):
+                s = s + qb[:, j:j + 16] @ kh[:, j:j + 16].T
+                if rounding == "emulate":
+                    s = _f32(s)
+                else:
+                    vs += _ulp32(s) ** 2 / 12.0
+            if rounding == "emulate":
+                p = _f32(torch.exp2(_f32(_f32(s * c) - l)))
+                acc.append(grouped(p, f32_sum=True))
+            else:
+                t = s * c - l
+                vt = c * c * vs + (_ulp32(s * c) ** 2 + _ulp32(t) ** 2) / 12.0
+                p = torch.exp2(t)
+                acc.append(grouped(p))
+                var.append(grouped(p * p * (ln2 * ln2 * vt + 2.0 * F32_ROUND ** 2 / 3.0)))
+        if q_group:
+            m = torch.cat(acc, 0)
+            v = torch.cat(var, 0) if var else None
+        else:
+            m = acc[0] if len(acc) == 1 else (torch.stack(acc).to(torch.float32).sum(0).double() if rounding == "emulate"
+                                               else torch.stack(acc).sum(0))
+            v = torch.stack(var).sum(0) if var else None
+        if rounding == "expected":
+            m = m + torch.sqrt(v + adds * (F32_ROUND * m) ** 2 / 3.0)
+        out.append(m)
+    return torch.stack(out)
+
+
+def mass_gate(name, got, ref64, fp32_eval, block):
+    """fp32 probability masses whose last dimension is keys, frames or key groups: rel-L2 of `got` against the float64 `ref64`
+    per block of `block` consecutive entries of the last dimension, separately for every leading index, within F32_SUM_BLOCK x a
+    floor from the same data - per block the largest of the rel-L2 of `fp32_eval` (a plain torch fp32 evaluation of the same
+    formula on the same operands), of `ref64` rounded to fp32 once, and of 2^-24 (one correct fp32 rounding: a block that torch
+    happens to hit exactly would otherwise have no floor).  A ragged last block of fewer than MASS_MIN_TAIL entries is merged
+    into the block before it.  `where` = (flattened leading index, block)."""
+    ref = f64(ref64)
+    n = ref.shape[-1]
+    ref = ref.reshape(-1, n)
+    nb = -(-n // block)
+    if nb > 1 and 0 < n % block < MASS_MIN_TAIL:
+        nb -= 1
+    bid = (torch.arange(n, device=ref.device) // block).clamp_max(nb - 1)
+
+    def sq(x):
+        return torch.zeros((ref.shape[0], nb), device=ref.device, dtype=torch.float64).index_add_(1, bid, x.square())
+
+    def rel(x):
+        return torch.sqrt(sq(f64(x).to(ref.device).reshape(-1, n) - ref) / sq(ref).clamp_min(1e-300))
+    fl = torch.maximum(rel(fp32_eval), rel(ref.to(torch.float32))).clamp_min(F32_ROUND)
+    ratio = rel(got) / fl
+    i = int(torch.argmax(ratio))
+    return Gate(name, float(ratio.view(-1)[i]), divmod(i, nb), rel_l2_t(f64(got).reshape(-1, n), ref) / float(fl.max()),
                 float(fl.max()), F32_SUM_BLOCK, None)

@@ -4,6 +4,7 @@ realistic defect planted: a stream-K unit that drops one of its 16 key pieces, o
 row's log-sum-exp off by 2e-4, one GEMM tile whose contraction stops short, a dK missing one 64-row query tile's contribution
 (the backward gate of test_gpu_backward_m64.py), a dW whose last split-K range is dropped or counted twice, LayerNorm rows whose
 statistics miss a chunk of 8 elements (the gate of test_gpu_layernorm_forms.py)."""
+import functools
 import math
 
 import numpy as np
@@ -12,6 +13,7 @@ import torch
 
 from oracle import memory_path as O
 from gpu_util import BWD_BLOCK, attention_bwd_ref64, attention_gate, floor_gate, gemm_gate, layernorm_gate, layernorm_ref64, round_to
+from gpu_util import DT, F32_SUM_BLOCK, attn_c32, lse2_offsets, mass_gate, prob_mass_eval, rel_l2_t
 
 R, S, H, HD = 8192, 512, 2, 64         # 64 128-query units per head; a unit's keys in 16 pieces of 32
 PIECES = 16
@@ -182,3 +184,126 @@ def test_layernorm_gate_rejects_rows_with_wrong_statistics(mode):
                 if d == 4096 and (mode == "fp16" or name == "last 8 residual elements missing" or
                                   (name == "dropped sum" and kind == "64 + N")):
                     assert not every.ok, str(every)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# mass_gate: the fp32 block gate of the kernels that sum softmax probabilities (tests/test_gpu_probability_mass.py)
+MS, MH, MHD, MP = 260, 2, 128, 52        # 260 keys: two 128-key blocks + 4 ragged keys, 8 blocks of 32 (+ 4), 5 frames of 52
+MQG, MKG = 28, 4                         # map cells: 28 query rows x 4 keys
+LN2 = math.log(2.0)
+
+
+@functools.lru_cache(maxsize=None)
+def _mass_case(R, mode):
+    """16-bit N(0,1) operands, the fp32 lse2 a stand-alone pass is handed (float64 log-sum-exp rounded to fp32 + a hashed offset
+    per row), and the float64 probabilities p [H, R, S] of the kernels' contract exp2(s c - lse2), built in blocks of 2048 rows"""
+    g = torch.Generator().manual_seed(9100 + R)
+    q = torch.randn((R, MH * MHD), generator=g).to(DT[mode])
+    k = torch.randn((MS, MH * MHD), generator=g).to(DT[mode])
+    c = attn_c32(np.float32(1.0) / np.sqrt(np.float32(MHD)))
+    s = torch.empty((MH, R, MS), dtype=torch.float64)
+    for h in range(MH):
+        sl = slice(h * MHD, (h + 1) * MHD)
+        for r0 in range(0, R, 2048):
+            s[h, r0:r0 + 2048] = q[r0:r0 + 2048, sl].double() @ k[:, sl].double().T
+    lse = (torch.logsumexp(s * (c * LN2), dim=2) / LN2).float() + lse2_offsets(MH, R)
+    p = torch.exp2(s * c - lse.double()[:, :, None])
+    return q, k, lse, c, s, p
+
+
+def _mass_defects(R, lse, c, s, p):
+    """column sums [H, S] (float64) of wrong kernels: the reference with one defect each, in head 1"""
+    col = p.sum(1)
+    last_tile = (R - 1) // 64 * 64                        # first row of the ragged last 64-query tile
+    out = {}
+
+    def edit(name, h, keys, delta):
+        bad = col.clone()
+        bad[h, keys] += delta
+        out[name] = bad
+    edit("last query row missing from a 32-key block", 1, slice(32, 64), -p[1, R - 1, 32:64])
+    edit("a row counted twice in a 32-key block", 1, slice(64, 96), p[1, 64, 64:96])
+    edit("a 64-query tile missing from a (128-key block, head) unit", 1, slice(128, 256), -p[1, 64:128, 128:256].sum(0))
+    edit("third plane (the last tile's rows) of a three-plane sum dropped", 1, slice(0, 128), -p[1, last_tile:, :128].sum(0))
+    r = next(r for r in range(65, R - 1) if abs(float(lse[1, r] - lse[1, r + 1])) >= 0.25)
+    edit("a row weighted with the lse2 of the row after it", 1, slice(0, MS),
+         torch.exp2(s[1, r] * c - lse[1, r + 1].double()) - p[1, r])
+    edit("a padded zero row added with the next head's lse2", 0, slice(128, 256),
+         torch.exp2(-lse[1, 0].double()).expand(128))
+    return col, out
+
+
+@pytest.mark.parametrize("mode", ["bf16", "fp16"])
+@pytest.mark.parametrize("R", [200, 12544])
+def test_mass_gate_resolves_one_query_row(R, mode):
+    """Column sums per block of 32 keys (one wave of attn_colsum3_kernel), frame scores per frame, map cells per key group.
+    Accepted: float64 rounded to fp32, the torch fp32 evaluation, and at R = 200 an fp32 evaluation that adds 64-row tiles in
+    order (another summation order).  Rejected at R = 200 and at R = 12 544, where one row is ~1e-4 of a column sum and the
+    whole-tensor gate of 1e-3 passes it: every defect of `_mass_defects`, a 4-key group credited to the next frame, a map
+    column rotated by one key group."""
+    q, k, lse, c, s, p = _mass_case(R, mode)
+    col, bad = _mass_defects(R, lse, c, s, p)
+    f32 = prob_mass_eval(q, k, lse, MH, MHD, c, torch.float32)
+    assert rel_l2_t(prob_mass_eval(q, k, lse, MH, MHD, c), col) < 1e-14
+    for name, got in (("float64 rounded to fp32", col.float()), ("torch fp32", f32)):
+        g = mass_gate(name, got, col, f32, 32)
+        print(g)
+        assert g.ok and g.worst <= 1.0 and g.floor < 1e-6, str(g)
+    if R == 200:
+        g = mass_gate("fp32, 64-row tiles added in order", prob_mass_eval(q, k, lse, MH, MHD, c, torch.float32, rows=64), col, f32, 32)
+        print(g)
+        assert g.ok, str(g)
+    for name, b in bad.items():
+        g = mass_gate(name, b.float(), col, f32, 32)
+        print(g, f"whole tensor rel-L2 {rel_l2_t(b, col):.1e}")
+        assert not g.ok and g.worst > 10 * F32_SUM_BLOCK, str(g)
+        if R == 12544 and "row" in name and "tile" not in name:
+            assert rel_l2_t(b, col) < 1e-3, name                  # a single row: under the whole-tensor gate
+    # a ragged last block of 4 keys is merged into the block before it: 8 blocks of 32, the last one 36 keys
+    b = col.clone()
+    b[1, -1] *= 1.0001
+    g = mass_gate("last key", b.float(), col, f32, 32)
+    assert not g.ok and g.where == (1, 7), str(g)
+
+    # frame scores: [F] = sum over heads and the frame's keys / P
+    frames = lambda x: x.view(MH, MS // MP, MP).sum(dim=(0, 2)) / MP
+    sc, sc32 = frames(col), frames(f32)
+    assert mass_gate("scores", sc.float(), sc, sc32, 1).ok
+    moved = p[:, :, 2 * MP - 4:2 * MP].sum() / MP                  # the last 4 keys of frame 1, all heads
+    b = sc.clone()
+    b[1] -= moved
+    b[2] += moved
+    g = mass_gate("a 4-key group credited to the next frame", b.float(), sc, sc32, 1)
+    print(g)
+    assert not g.ok and g.where[1] in (1, 2), str(g)
+    b = sc.clone()
+    b[4] -= p[:, R - 1, 4 * MP:].sum() / MP
+    g = mass_gate("last query row missing from the last frame", b.float(), sc, sc32, 1)
+    print(g)
+    assert not g.ok and g.where == (0, 4), str(g)               # (blocks of one entry: the last one is no ragged tail)
+
+    # maps: [H, query groups, key groups]
+    m64 = prob_mass_eval(q, k, lse, MH, MHD, c, torch.float64, MQG, MKG)
+    m32 = prob_mass_eval(q, k, lse, MH, MHD, c, torch.float32, MQG, MKG)
+    assert tuple(m64.shape) == (MH, -(-R // MQG), MS // MKG) and rel_l2_t(m64.sum(1), col.view(MH, -1, MKG).sum(2)) < 1e-14
+    assert mass_gate("map", m64.float(), m64, m32, 1).ok
+    b = m64.clone()
+    b[1, 3] = torch.roll(b[1, 3], -1)                              # output column j holds key group j + 1
+    g = mass_gate("a map row rotated by one key group", b.float(), m64, m32, 1)
+    print(g)
+    assert not g.ok and g.where[0] == 1 * m64.shape[1] + 3, str(g)
+    # one query row per cell: a block is a single exponent and torch's own error is no floor for another correct evaluation;
+    # the expected magnitude of the fp32 rounding points is.  The emulation that rounds where the kernels round passes it at 2.7 .. 3.6 x
+    # (against torch's floor it reads 8.5 .. 10.4 x), and a rotated row is rejected
+    one64 = prob_mass_eval(q, k, lse, MH, MHD, c, torch.float64, 1, MKG)
+    one32 = prob_mass_eval(q, k, lse, MH, MHD, c, torch.float32, 1, MKG)
+    emu = prob_mass_eval(q, k, lse, MH, MHD, c, torch.float64, 1, MKG, rounding="emulate")
+    exp = prob_mass_eval(q, k, lse, MH, MHD, c, torch.float64, 1, MKG, rounding="expected", adds=MKG // 4 + 8)
+    g = mass_gate("one-row cells, expected-rounding floor: the emulation", emu, one64, exp, 1)
+    print(g, mass_gate("... against the torch floor", emu, one64, one32, 1), sep="\n")
+    assert g.ok and g.worst > 1.0 and g.floor < 1e-4, str(g)      # of the size of a correct evaluation's error, not far above
+    # (torch's CPU GEMM rounds after every one of the 128 products, not after 8 steps of 16: up to ~10 x this floor, printed)
+    print(mass_gate("one-row cells, expected-rounding floor: torch fp32", one32, one64, exp, 1))
+    b = one64.clone()
+    b[1, 3] = torch.roll(b[1, 3], -1)
+    assert not mass_gate("one-row cells, a rotated row", b.float(), one64, exp, 1).ok
