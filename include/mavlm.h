@@ -440,10 +440,24 @@ int mavlm_attention_batch(const void* Q, int32_t ldq, const void* K, int32_t ldk
  * and 128-query block; no stream-K, no split-KV, no workspace): video b's rows of O and lse2 equal, bit for bit, mavlm_attention
  * on that video's own operands.  All arguments are checked before anything is enqueued: MAVLM_E_ARG for a null pointer, nb < 1,
  * nb > 16, H % nb != 0, S[b] < 1, kv_off[b] < 0 or not a multiple of 8, key ranges [kv_off[b], kv_off[b] + S[b] * ld) that
- * overlap (by ldk or by ldv), bad strides; MAVLM_E_SHAPE for head_dim > 128 (448 included: one mavlm_attention_hd per video). */
+ * overlap (by ldk or by ldv), bad strides; MAVLM_E_SHAPE for head_dim > 128 (448 included: one mavlm_attention_hd per video, or
+ * mavlm_attention_hd_batch_varlen below). */
 int mavlm_attention_batch_varlen(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, void* O,
                                  int32_t ldo, float* lse2, int32_t R, const int32_t* S, const int64_t* kv_off, int32_t H,
                                  float scale, int32_t nb, int32_t head_dim, int32_t dtype, void* stream);
+/* The same for heads of 448 columns (the 32-query-wave forward): ONE launch over (video, head, 128-query block) instead of one
+ * mavlm_attention_hd per video.  Same parameter list and layouts: Q / O [nb*R, >= Hv*448] with Hv = H / nb, K / V packed, video b's
+ * S[b] >= 1 keys kv_off[b] elements into them, lse2 [H, R] (may be null).  Always the plain grid, no workspace, no atomics, one
+ * owner per output row.  Guarantee: video b's rows of O and lse2 carry, bit for bit, what mavlm_attention_hd (no workspace, i.e.
+ * the plain grid) gives on that video's operands alone; a ragged last key tile reads zeros, never the next video's rows.
+ * All arguments are checked before anything is enqueued: MAVLM_E_ARG for a null pointer, nb < 1, nb > 16, H % nb != 0, S[b] < 1,
+ * kv_off[b] < 0 or not a multiple of 8, overlapping key ranges (by ldk or by ldv), strides that are no multiple of 8 (ldo: 4) or
+ * shorter than Hv*448, Q / K / V not 16-byte (O: 8-byte) aligned, or a video whose (S[b] + 64) * ld * 2 bytes pass the kernel's
+ * 32-bit offsets; MAVLM_E_SHAPE for a head_dim other than 448, and while mavlm_set_attention_wide_groups(1) is in force (the
+ * 16-query-wave kernel has no such form). */
+int mavlm_attention_hd_batch_varlen(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, void* O,
+                                    int32_t ldo, float* lse2, int32_t R, const int32_t* S, const int64_t* kv_off, int32_t H,
+                                    float scale, int32_t nb, int32_t head_dim, int32_t dtype, void* stream);
 int mavlm_attention_colsum_hd(const void* Q, int32_t ldq, const void* K, int32_t ldk, const float* lse2, float* part,
                               int32_t R, int32_t S, int32_t H, int32_t head_dim, float scale, int32_t dtype, void* stream);
 /* part[H,S] fp32 = column sums over queries of the normalised probabilities.  MemoryController.py:135
@@ -641,6 +655,11 @@ int mavlm_set_attention_colsum_wgs(int32_t wgs);
  * its deferred rescales as one group and adds the fp32 row sums in a different order (results agree to the tolerance of the
  * oracle tests, not bit for bit). */
 int mavlm_set_attention_wide_groups(int32_t groups);
+/* mavlm_step_batch_frames at heads of 448 columns: 0 (DEFAULT) = every formation layer runs one plain-grid forward per video;
+ * 1 = one variable-length launch over all active videos (mavlm_attention_hd_batch_varlen; falls back to the per-video launches
+ * while mavlm_set_attention_wide_groups(1) is in force).  Same bits either way; the frame scores keep their per-video column-sum
+ * pass.  Accepts 0 / 1; process-wide, read at the next step. */
+int mavlm_set_attention_hd_varlen(int32_t on);
 /* how mavlm_step obtains the frame scores of the last formation layer (patches % 4 == 0, <= 64 frames per chunk): 1 (default) =
  * fused into that layer's attention forward - heads of <= 128 columns: every query row carries the probability mass of the
  * current frame next to its row sum; heads of 448 (round 4): the forward writes one log-mass entry per query row and 32-key tile,

@@ -166,6 +166,9 @@ SIGNATURES = {
                                                C.c_float, i32, vp]),
     "mavlm_attention_batch_varlen": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, C.POINTER(i32), C.POINTER(C.c_int64),
                                                i32, C.c_float, i32, i32, i32, vp]),
+    "mavlm_attention_hd_batch_varlen": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, C.POINTER(i32), C.POINTER(C.c_int64),
+                                                  i32, C.c_float, i32, i32, i32, vp]),
+    "mavlm_set_attention_hd_varlen": (C.c_int, [i32]),
     "mavlm_attention_colsum_batch_varlen_floats": (C.c_int64, [i32, C.POINTER(i32), i32, i32]),
     "mavlm_attention_colsum_batch_varlen": (C.c_int, [vp, i32, vp, i32, C.POINTER(C.c_int64), vp, vp, C.c_int64, i32,
                                                       C.POINTER(i32), i32, i32, i32, C.c_float, i32, vp]),

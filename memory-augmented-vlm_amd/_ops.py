@@ -465,6 +465,37 @@ def attention_batch_varlen(q, k, v, heads, key_counts, want_lse=False, head_dim=
     return out, lse
 
 
+def attention_hd_batch_varlen(q, k, v, heads, key_counts, want_lse=False, scale=None):
+    """`attention_batch_varlen` for heads of 448 columns (`mavlm_attention_hd_batch_varlen`): q [nb*R, >=heads*448], k / v
+    [sum(key_counts), >=heads*448] packed back to back (same row stride for both).  ONE plain-grid launch: video b's rows equal
+    `mavlm_attention_hd` (no workspace) on its own operands bit for bit.
+    Returns (ctx [nb*R, heads*448], lse2 [nb*heads, R] fp32 | None)."""
+    _need_gpu(q, k, v)
+    nb = len(key_counts)
+    RB, _, ldq = _rows(q)
+    ldk, offs = _kv_varlen(k, key_counts, "attention_hd_batch_varlen")
+    ldv, _ = _kv_varlen(v, key_counts, "attention_hd_batch_varlen")
+    W = heads * 448
+    if RB % nb or ldv != ldk or q.shape[1] < W or k.shape[1] < W or v.shape[1] < W or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise capi.MavlmError("attention_hd_batch_varlen: operand mismatch (stacked query rows, packed K / V with one row stride)")
+    R, H = RB // nb, heads * nb
+    out = torch.empty((RB, W), device=q.device, dtype=q.dtype)
+    lse = torch.empty((H, R), device=q.device, dtype=torch.float32) if want_lse else None
+    capi.check(capi.lib().mavlm_attention_hd_batch_varlen(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(),
+                                                          out.stride(0), lse.data_ptr() if want_lse else None, R, _i32s(key_counts),
+                                                          _i64s(offs), H, 1.0 / math.sqrt(448.0) if scale is None else float(scale),
+                                                          nb, 448, dtype_code(q.dtype), stream_ptr()),
+               "mavlm_attention_hd_batch_varlen")
+    return out, lse
+
+
+def set_attention_hd_varlen(on):
+    """Switch of the clip step (`step_frames`) at heads of 448 columns, process-wide, OFF by default: on = every formation layer
+    runs one variable-length launch over the active videos (`mavlm_set_attention_hd_varlen`), off = one launch per video.  Same
+    bits either way."""
+    capi.check(capi.lib().mavlm_set_attention_hd_varlen(1 if on else 0), "mavlm_set_attention_hd_varlen")
+
+
 def attention_colsum_batch_varlen(q, k, lse2, heads, key_counts, head_dim=128, scale=None):
     """`attention_colsum_batch` for videos of different key counts in ONE launch (`mavlm_attention_colsum_batch_varlen`): operands
     as `attention_batch_varlen`, lse2 [nb*heads, R] as it returns it.  Every video runs the single-video schedule of its own shape:

@@ -313,7 +313,18 @@ struct hd_sk_plan {
 // plain grid, split-KV, levelled stream-K: pieces own disjoint tile ranges - so nothing has to be merged; frame_tiles_kernel, which runs
 // after the row's final log-sum-exp is known, turns the entries into partial frame sums, frame_finish_kernel (attention3.hip) adds
 // them in a fixed order.  O and lse2 are bit-identical to the FT = 0 kernel (the row sums keep their order).
-template <typename T, int HD, int KPF, int VPF, int FT = 0>
+//
+// VL: the variable-length row batch (clip row batches; plain grid only, FT = 0).  blockIdx.z is the video; its key count is
+// vl.S[video] and its keys start vl.off[video] elements into K / V - the two by-value arrays replace S_all and video * kv_bs, which
+// are not read.  Everything a segment derives from the key count (its tiles, the descriptors' end, the ragged last tile, the K tile
+// that runs ahead of V) is per segment already and head_rsrc ends the descriptor behind the video's last key, so a workgroup runs
+// exactly what the plain grid of a single launch over that video's operands runs - the same bits - and never reads the next
+// video's first rows although the keys are packed back to back.  The arrays are indexed by the workgroup-uniform blockIdx.z and
+// stay in the kernel-argument segment (scalar loads, no private copy).  The instantiations without VL take an empty argument.
+template <bool VL> struct attn_hd_vl_arg {};
+template <> struct attn_hd_vl_arg<true> { int S[MAVLM_VBASE_MAX]; long long off[MAVLM_VBASE_MAX]; };
+
+template <typename T, int HD, int KPF, int VPF, int FT = 0, bool VL = false>
 __global__ __launch_bounds__(256, 1) void attn_fwd_hd2_kernel(const uint16_t* __restrict__ Qa, int ldq,
                                                               const uint16_t* __restrict__ Ka, int ldk,
                                                               const uint16_t* __restrict__ Va, int ldv,
@@ -321,7 +332,9 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_hd2_kernel(const uint16_t* __
                                                               int R, int S_all, int H, float c, float* __restrict__ Opart,
                                                               float* __restrict__ lse_part, int tps, long long kv_bs,
                                                               hd_sk_plan plan, float* __restrict__ fent = nullptr, int FPK = 0,
-                                                              int HA = 0) {
+                                                              int HA = 0, attn_hd_vl_arg<VL> vl = {}) {
+  static_assert(!VL || FT == 0, "the variable-length form is the plain grid of the forward without frame entries");
+  if constexpr (VL) S_all = vl.S[blockIdx.z];                 // (plain grid only: one whole-unit segment of video blockIdx.z)
   constexpr int NSUB = (HD + 127) / 128;
   constexpr int SUB = KTH * 256;
   constexpr int TILE = NSUB * SUB;
@@ -394,8 +407,12 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_hd2_kernel(const uint16_t* __
   const int vb = hg / H, h = hg - vb * H;                      // video of the row batch, head inside it
   const uint16_t* const Q = Qa + (size_t)vb * R * ldq;
   uint16_t* const O = Oa + (size_t)vb * R * ldo;
-  const uint16_t* const K = Ka + (size_t)vb * kv_bs + (size_t)t_lo * KTH * ldk;
-  const uint16_t* const V = Va + (size_t)vb * kv_bs + (size_t)t_lo * KTH * ldv;
+  auto video_keys = [&](const uint16_t* p) {                   // where the video's keys start
+    if constexpr (VL) return p + (size_t)vl.off[blockIdx.z];
+    else return p + (size_t)vb * kv_bs;
+  };
+  const uint16_t* const K = video_keys(Ka) + (size_t)t_lo * KTH * ldk;
+  const uint16_t* const V = video_keys(Va) + (size_t)t_lo * KTH * ldv;
   float* const lse2 = lse2a != nullptr ? lse2a + (size_t)vb * H * R : nullptr;
   const int S = (S_all - t_lo * KTH < nt * KTH) ? S_all - t_lo * KTH : nt * KTH;      // keys of this segment
   const int q0 = qblk * 128 + wave * 32;
@@ -1048,7 +1065,8 @@ hipError_t launch_fwd_hd(const mavlm_attn_args& a, hipStream_t s) {
       mavlm_prof_scope prof(MAVLM_K_ATTN, 4.0 * a.R * (double)a.S * a.H * HD, 2.0 * HD * a.H * (2.0 * a.R + 2.0 * a.S), s);
       hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, (const uint16_t*)a.Q, a.ldq, (const uint16_t*)a.K, a.ldk,
                          (const uint16_t*)a.V, a.ldv, (uint16_t*)a.O, a.ldo, a.lse2, a.R, a.S, Hv, c, opart, lpart, tps,
-                         (long long)a.kv_bstride, plan, FT ? a.frame_scr : (float*)nullptr, FT ? a.frame_keys : 0, a.H);
+                         (long long)a.kv_bstride, plan, FT ? a.frame_scr : (float*)nullptr, FT ? a.frame_keys : 0, a.H,
+                         attn_hd_vl_arg<false>{});
     }
     if (plan.wgs > 0) {
       int cut = 0;
@@ -1138,6 +1156,7 @@ int mavlm_attention_hd_streamk(int R, int S, int H, int head_dim, int info[3]) {
 }
 
 int g_mavlm_attn_hd_qg = 0;      // tuning hook: 0 = automatic (32-query waves at head_dim 448), 1 = 16-query waves, 2 = 32-query
+int g_mavlm_attn_hd_varlen = 0;  // mavlm_set_attention_hd_varlen: the clip step's formation layers at head_dim 448 in one launch
 hipError_t mavlm_launch_attention_hd(const mavlm_attn_args& a, int head_dim, int dtype, hipStream_t s) {
   const bool f16 = dtype == MAVLM_F16;
   if (head_dim == 448) {
@@ -1149,6 +1168,47 @@ hipError_t mavlm_launch_attention_hd(const mavlm_attn_args& a, int head_dim, int
   if (head_dim == 256) return f16 ? launch_fwd_hd<F16, 256, 1>(a, s) : launch_fwd_hd<BF16, 256, 1>(a, s);
   if (head_dim == 224) return f16 ? launch_fwd_hd<F16, 224, 1>(a, s) : launch_fwd_hd<BF16, 224, 1>(a, s);
   return hipErrorInvalidValue;
+}
+
+// Variable-length row batch at head_dim 448 (32-query waves only): video b attends to its own a.vl_S[b] keys, which start
+// a.vl_off[b] elements into K / V (host arrays, read here; they travel by value).  Always the plain grid - one workgroup per
+// (video, head, 128-query block), every output row has one owner, no partials, no merge, a.split_ws is not read: video b's rows
+// of O / lse2 carry the bits of the plain-grid launch (mavlm_launch_attention_hd, no workspace) over that video's operands alone.
+// ONE profile scope whose flops and bytes are the sums of what those nb launches report.
+hipError_t mavlm_launch_attention_hd_varlen(const mavlm_attn_args& a, int head_dim, int dtype, hipStream_t s) {
+  const int nb = a.nb;
+  if (head_dim != 448 || g_mavlm_attn_hd_qg == 1) return hipErrorInvalidValue;
+  if (!a.vl_S || !a.vl_off || nb < 1 || nb > MAVLM_VBASE_MAX || a.H <= 0 || a.H % nb != 0 || a.R <= 0) return hipErrorInvalidValue;
+  attn_hd_vl_arg<true> vl = {};
+  double keys = 0.0;
+  for (int b = 0; b < nb; ++b) {
+    // the kernel addresses a video's keys with 32-bit byte offsets (tile * 32 * ld * 2 + the lane's row), and the K ring asks for
+    // one 32-key tile behind the last one (it reads zeros there): the ragged last tile + that tile stay below 2^31
+    const double reach = (double)a.vl_S[b] + 2.0 * KTH;
+    if (a.vl_S[b] < 1 || a.vl_off[b] < 0 || reach * a.ldk * 2.0 >= 2147483648.0 || reach * a.ldv * 2.0 >= 2147483648.0)
+      return hipErrorInvalidValue;
+    vl.S[b] = a.vl_S[b];
+    vl.off[b] = a.vl_off[b];
+    keys += a.vl_S[b];
+  }
+  constexpr int HD = 448;
+  constexpr int LDS = 4 * ((HD + 127) / 128) * KTH * 256;
+  const int Hv = a.H / nb;
+  const dim3 grid(((a.R + 127) / 128) * Hv, 1, nb);
+  const float c = a.scale * 1.44269504088896340736f;
+  const hd_sk_plan plan = {};
+  auto launch = [&](auto kern) {
+    static mavlm_per_device_once once;
+    hipError_t e = once.dyn_lds((const void*)kern, LDS);
+    if (e != hipSuccess) return e;
+    mavlm_prof_scope prof(MAVLM_K_ATTN, 4.0 * a.R * keys * Hv * HD, 2.0 * HD * Hv * (2.0 * a.R * nb + 2.0 * keys), s);
+    hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, (const uint16_t*)a.Q, a.ldq, (const uint16_t*)a.K, a.ldk,
+                       (const uint16_t*)a.V, a.ldv, (uint16_t*)a.O, a.ldo, a.lse2, a.R, 0, Hv, c, (float*)nullptr, (float*)nullptr, 0,
+                       0ll, plan, (float*)nullptr, 0, a.H, vl);
+    return hipGetLastError();
+  };
+  if (dtype == MAVLM_F16) return launch(attn_fwd_hd2_kernel<F16, HD, 3, 3, 0, true>);
+  return launch(attn_fwd_hd2_kernel<BF16, HD, 3, 3, 0, true>);
 }
 
 // Forward + frame scores in one pass at head_dim 448 (attn_fwd_hd2_kernel<.., FT = 1> + frame_tiles_kernel; the caller finishes with

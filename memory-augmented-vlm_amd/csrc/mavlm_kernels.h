@@ -265,6 +265,11 @@ hipError_t mavlm_launch_colsum(const mavlm_colsum_args& a, int dtype, hipStream_
 hipError_t mavlm_launch_colsum3(const mavlm_colsum_args& a, int dtype, hipStream_t s);   // pipelined (attention3.hip)
 // wide heads (attention_hd.hip): head_dim 448 (OV-7B), also 128 for cross-checks; columns of head h start at h*head_dim
 hipError_t mavlm_launch_attention_hd(const mavlm_attn_args& a, int head_dim, int dtype, hipStream_t s);
+// variable-length row batch of the 32-query-wave forward (a.vl_S / a.vl_off as mavlm_launch_attention3_varlen reads them): ONE
+// plain-grid launch over (video, head, 128-query block); head_dim 448 only and not under g_mavlm_attn_hd_qg == 1 - anything
+// else is hipErrorInvalidValue.  Video b's rows carry the bits of mavlm_launch_attention_hd (no workspace) on its operands alone.
+hipError_t mavlm_launch_attention_hd_varlen(const mavlm_attn_args& a, int head_dim, int dtype, hipStream_t s);
+extern int g_mavlm_attn_hd_varlen;   // mavlm_step_batch_frames at head_dim 448: 1 = that launch, 0 (default) = one launch per video
 hipError_t mavlm_launch_colsum_hd(const mavlm_colsum_args& a, int head_dim, int dtype, hipStream_t s);
 
 // attention maps (attention_maps.hip): out[h][i][j] = sum over the rows of query group i and the keys of key group j of

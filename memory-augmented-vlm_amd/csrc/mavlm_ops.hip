@@ -127,6 +127,7 @@ int mavlm_set_attention_streamk_min_tiles(int32_t tiles) { return set_hook(&g_ma
 int mavlm_set_attention_streamk_waves(int32_t waves) { return set_hook(&g_mavlm_attn_sk_waves, waves, waves == 0 || waves == 4 || waves == 8); }
 int mavlm_set_attention_colsum_wgs(int32_t wgs) { return set_hook(&g_mavlm_colsum_wgs, wgs, wgs == 0 || (wgs >= 64 && wgs <= 1024)); }
 int mavlm_set_attention_wide_groups(int32_t groups) { return set_hook(&g_mavlm_attn_hd_qg, groups, groups >= 0 && groups <= 2); }
+int mavlm_set_attention_hd_varlen(int32_t on) { return set_hook(&g_mavlm_attn_hd_varlen, on, on == 0 || on == 1); }
 // (2: diagnostics - the tile-entry form wherever it is supported)
 int mavlm_set_frame_score_mode(int32_t mode) { return set_hook(&g_mavlm_frame_score_mode, mode, mode >= 0 && mode <= 2); }
 int mavlm_set_gemm_short_splits(int32_t splits) { return set_hook(&g_mavlm_gemm_f32_short_splits, splits, splits >= 1 && splits <= 8); }
@@ -329,6 +330,28 @@ int mavlm_attention_batch_varlen(const void* Q, int32_t ldq, const void* K, int3
   mavlm_attn_args a = attn_args(Q, ldq, K, ldk, V, ldv, O, ldo, lse2, R, 0, H, scale);
   a.nb = nb; a.vl_S = S; a.vl_off = off;
   return api_rc(mavlm_launch_attention3_varlen(a, dtype, (hipStream_t)stream));
+}
+
+// the same at head_dim 448 (32-query waves): ONE plain-grid launch over (video, head, 128-query block)
+int mavlm_attention_hd_batch_varlen(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, void* O,
+                                    int32_t ldo, float* lse2, int32_t R, const int32_t* S, const int64_t* kv_off, int32_t H,
+                                    float scale, int32_t nb, int32_t head_dim, int32_t dtype, void* stream) {
+  // every check comes before the launch
+  if (!Q || !K || !V || !O || R <= 0 || nb < 1 || nb > MAVLM_VBASE_MAX || H <= 0 || H % nb != 0 || (dtype != 0 && dtype != 1))
+    return MAVLM_E_ARG;
+  if (head_dim != 448 || g_mavlm_attn_hd_qg == 1) return MAVLM_E_SHAPE;      // (the 16-query-wave kernel has no such form)
+  const int Hv = H / nb;
+  if ((ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 3) || ldq < Hv * 448 || ldk < Hv * 448 || ldv < Hv * 448 || ldo < Hv * 448)
+    return MAVLM_E_ARG;
+  if ((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V) & 15) || ((uintptr_t)O & 7)) return MAVLM_E_ARG;   // 16-byte loads, 8-byte stores
+  if (varlen_ranges_bad(S, kv_off, nb, ldk) || varlen_ranges_bad(S, kv_off, nb, ldv)) return MAVLM_E_ARG;
+  for (int b = 0; b < nb; ++b)     // 32-bit byte offsets inside a video's keys, one 32-key tile past the ragged last one included
+    if (((double)S[b] + 64.0) * ldk * 2.0 >= 2147483648.0 || ((double)S[b] + 64.0) * ldv * 2.0 >= 2147483648.0) return MAVLM_E_ARG;
+  long long off[MAVLM_VBASE_MAX];
+  for (int b = 0; b < nb; ++b) off[b] = kv_off[b];
+  mavlm_attn_args a = attn_args(Q, ldq, K, ldk, V, ldv, O, ldo, lse2, R, 0, H, scale);
+  a.nb = nb; a.vl_S = S; a.vl_off = off;
+  return api_rc(mavlm_launch_attention_hd_varlen(a, head_dim, dtype, (hipStream_t)stream));
 }
 
 // ---- column sums and attention maps ------------------------------------------------------------------------------------------

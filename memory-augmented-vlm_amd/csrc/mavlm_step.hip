@@ -86,9 +86,13 @@ int attn_block(mavlm_ctx* x, hipStream_t s, const mavlm_attn_weights& aw, const 
     a.frame_out = p_fout(x);
     a.frame_keys = c.patches;
   }
-  if (vl_S && wide_heads(c)) {
-    // head_dim 448 has no variable-length kernel: one launch of the forward per video, plain grid (the stacked GEMMs around it
-    // are where a row batch gains at this width)
+  if (vl_S && wide_heads(c) && g_mavlm_attn_hd_varlen && c.hidden / c.heads == 448 && g_mavlm_attn_hd_qg != 1) {
+    // opt-in (mavlm_set_attention_hd_varlen): ONE plain-grid launch over the B active videos - the bits of the loop below
+    a.vl_S = vl_S; a.vl_off = vl_off; a.split_ws = nullptr;
+    MAVLM_TRY(mavlm_launch_attention_hd_varlen(a, 448, dt, s));
+  } else if (vl_S && wide_heads(c)) {
+    // the default at head_dim 448 (and the only form of the 16-query-wave kernel): one launch of the forward per video, plain
+    // grid (the stacked GEMMs around it are where a row batch gains at this width)
     for (int b = 0; b < B; ++b) {
       mavlm_attn_args a1 = a;
       a1.Q = (const char*)a.Q + (size_t)b * R1 * Dp * 2;

@@ -1404,10 +1404,14 @@ class LlavaMetaForCausalLM:
         The other row-batched emits take every hidden size that is a multiple of 128; the clip emit (a fine-frame count per
         video, `mavlm_fuse_emit_layout_frames_to`) still needs a multiple of 256 (D = 896: `MavlmError` before any step).
         Measured 1.23 x at D = 1024 and 0.96 x (slower) at D = 3584 with 4 clips: hence off by default.
+        At heads of 448 columns (D = 3584) a clip step runs one attention launch per video; the process-wide switch
+        `_ops.set_attention_hd_varlen(True)` (`mavlm_set_attention_hd_varlen`, OFF by default, same bits) makes it one
+        variable-length launch per formation layer - measured 1.10 x against single videos with those 4 clips.  This method does
+        not touch that switch.
         `training=True` additionally groups the clips of a forward under autograd that way (off by default, also with `on`): a
         group takes one `BatchedProjector.step_train_frames` - the variable-length attention forward and backward - and
         `video_memory_tokens_clips_train` builds its blocks, at every hidden size of the training path (896 included).  Heads
-        of 448 columns have no variable-length attention: at that width the training grouping stays as it is with the switch
+        of 448 columns have no variable-length attention backward: at that width the training grouping stays as it is with the switch
         off.  `on=False` switches both off."""
         self._clip_row_batches = bool(on)
         self._clip_row_batches_train = bool(on) and bool(training)
