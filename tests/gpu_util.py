@@ -124,6 +124,71 @@ def layernorm_gate(name, out, ref, mode):
     return floor_gate(name, out, ref, LN_ROWS, ref.shape[1], mode, BWD_BLOCK)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# Fused dense + residual + LayerNorm GEMM (EPI_LN of csrc/gemm256.hip and gemm128.hip): inputs whose rows cannot stand in for one
+# another, and the gate per LN_ROWS rows x one 256-column tile.  On plain N(0,1) operands the 256-column tile means of a row
+# differ by sigma / 16 only, and a row that drops the between-tile term of the merge, or reads a partner's statistics at another
+# row, stays under the block limit (tests/test_gates_cpu.py shows it).  Planted: row r of the residual is scaled by s(r) in
+# {1/4, 1/2, 1, 2, 4}, and its 256 columns of tile t are shifted by o(r, t) s(r), o a multiple of FUSED_LN_UNIT in [-4, 4].
+FUSED_LN_UNIT = 0.5                    # spacing of the tile offsets (exact on both 16-bit grids, as is every offset)
+FUSED_LN_DISTANCES = (1, 16, 112, 128, 224, 256)     # neighbour row, 16-row fragment, half tile of each height, tile
+_FUSED_LN_PERM = (5, 12, 0, 9, 16, 3, 7, 14, 1, 10, 4, 15, 8, 2, 13, 6, 11)      # a fixed permutation of 0 .. 16
+
+
+def _hash_idx(i, salt, mod):
+    """hashed index in [0, mod) of the int64 tensor i (Knuth's multiplier, two folds; no int64 overflow below i = 2^31)"""
+    h = i * 2654435761 + salt * 40503
+    return ((h >> 11) ^ (h >> 23) ^ (h >> 5)) % mod
+
+
+def fused_ln_pattern(M, ntn, device="cpu"):
+    """(scale index [M] in 0 .. 4, offset index [M, ntn] in 0 .. 16) of the planted residual: s(r) = 2^(index - 2),
+    o(r, t) = (index - 8) x FUSED_LN_UNIT.  The scale is hashed per row.  The offsets of row r are PERM[(r + t step(r)) mod 17]
+    with a hashed step(r) in 1 .. 16 and a fixed permutation PERM of 0 .. 16: the (up to 16) tiles of a row all differ (17 is
+    prime), so a tile's statistics taken from another tile of the row are wrong ones; and tile 0 holds PERM[r mod 17], which
+    differs between rows r and r + d at every d of FUSED_LN_DISTANCES (none is a multiple of 17) - hashed values alone, 5 x 17 of
+    them, could not keep the 48 897 rows of a single tile apart from their neighbours."""
+    r = torch.arange(M, dtype=torch.int64, device=device)
+    s_idx = _hash_idx(r, 1, 5)
+    step = 1 + _hash_idx(r, 2, 16)
+    t = torch.arange(ntn, dtype=torch.int64, device=device)
+    o_idx = torch.tensor(_FUSED_LN_PERM, dtype=torch.int64, device=device)[(r[:, None] + t[None, :] * step[:, None]) % 17]
+    return s_idx, o_idx
+
+
+def fused_ln_inputs(M, N, K, mode, seed, planted=True, device="cuda"):
+    """x [M, K], w [N, K], b [N] fp32, res [M, N], gamma [N] fp32, beta [N] fp32 on `device`, distributed as the `_ln_case` of
+    tests/test_gpu_batch.py makes them (x and res N(0,1), w uniform within 1 / sqrt(K), b and beta within 0.1, gamma within 0.1
+    of 1; 16-bit operands on the grid of `mode`).  `planted`: res = round16(N(0,1) + o(r, t)) s(r), see `fused_ln_pattern`."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    randn = lambda *shape: torch.randn(shape, generator=g, device=device)
+    uni = lambda n, a: (torch.rand((n,), generator=g, device=device) * 2.0 - 1.0) * a
+    x = randn(M, K).to(DT[mode])
+    w = ((torch.rand((N, K), generator=g, device=device) * 2.0 - 1.0) / math.sqrt(K)).to(DT[mode])
+    b = uni(N, 0.1)
+    res = randn(M, N)
+    if planted:
+        s_idx, o_idx = fused_ln_pattern(M, N // 256, device)
+        off = ((o_idx - 8).to(torch.float32) * FUSED_LN_UNIT).repeat_interleave(256, dim=1)
+        res = (res + off).to(DT[mode]) * torch.exp2((s_idx - 2).to(torch.float32)).to(DT[mode])[:, None]     # (x 2^k: exact)
+    else:
+        res = res.to(DT[mode])
+    return x, w, b, res, 1.0 + uni(N, 0.1), uni(N, 0.1)
+
+
+def fused_ln_ref64(x, w, b, res, gamma, beta, eps):
+    """LayerNorm64(x.double() @ w.double().T + b + res) * gamma + beta on the operands' device: the reference of the fused
+    kernel - float64 throughout, never another kernel's output."""
+    return layernorm_ref64(x.double() @ w.double().T + b.double(), res, gamma, beta, eps)
+
+
+def fused_ln_gate(out, ref64, mode):
+    """Fused dense + residual + LayerNorm: `out` within BWD_BLOCK x floor per block of LN_ROWS rows x 256 columns (one row group
+    of one workgroup's column tile), the floor being `ref64` rounded once to the output grid.  The kernel computes in fp32 and
+    rounds once: the expected ratio is 1.0.  `where` = (row block, column tile)."""
+    return floor_gate("fused dense+LN", out, ref64, LN_ROWS, 256, mode, BWD_BLOCK)
+
+
 def attention_gate(ctx, lse2, ref_ctx, ref_lse2, heads, mode):
     """Forward attention: ctx within ATTN_UNIT x floor per (128-query unit, head) and ATTN_WHOLE x floor over the tensor; lse2
     (log2 domain, [H, R]) within LSE2_ATOL of the reference on every row.  Returns (gate, worst lse2 error, passed)."""

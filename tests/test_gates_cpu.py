@@ -3,7 +3,8 @@ accept a correctly rounded result.  Reduced shapes, numpy float64 references; th
 realistic defect planted: a stream-K unit that drops one of its 16 key pieces, one unit whose merge weight is off by 2^-6, one
 row's log-sum-exp off by 2e-4, one GEMM tile whose contraction stops short, a dK missing one 64-row query tile's contribution
 (the backward gate of test_gpu_backward_m64.py), a dW whose last split-K range is dropped or counted twice, LayerNorm rows whose
-statistics miss a chunk of 8 elements (the gate of test_gpu_layernorm_forms.py)."""
+statistics miss a chunk of 8 elements (the gate of test_gpu_layernorm_forms.py), and the defects a row of the fused dense + residual +
+LayerNorm epilogue can have on its own (the gate of test_gpu_fused_layernorm.py; a restatement of that epilogue in fp32)."""
 import functools
 import math
 
@@ -14,6 +15,7 @@ import torch
 from oracle import memory_path as O
 from gpu_util import BWD_BLOCK, attention_bwd_ref64, attention_gate, floor_gate, gemm_gate, layernorm_gate, layernorm_ref64, round_to
 from gpu_util import DT, F32_SUM_BLOCK, attn_c32, lse2_offsets, mass_gate, prob_mass_eval, rel_l2_t
+from gpu_util import block_rel_l2, fused_ln_gate, fused_ln_inputs, fused_ln_pattern, fused_ln_ref64
 
 R, S, H, HD = 8192, 512, 2, 64         # 64 128-query units per head; a unit's keys in 16 pieces of 32
 PIECES = 16
@@ -307,3 +309,118 @@ def test_mass_gate_resolves_one_query_row(R, mode):
     b = one64.clone()
     b[1, 3] = torch.roll(b[1, 3], -1)
     assert not mass_gate("one-row cells, a rotated row", b.float(), one64, exp, 1).ok
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# fused_ln_gate: the fused dense + residual + LayerNorm epilogue (EPI_LN of csrc/gemm256.hip), restated from its description - per
+# 256-column tile the mean and the centred sum of squares of a row, Chan's merge of the tiles in tile order, the normalisation -
+# in fp32 (what the kernel computes) or float64, with one defect in ONE row where asked
+FL_M, FL_K = 96, 64
+FL_ROW = 37                      # the row the single-row defects sit in: block 9 of the 4-row blocks
+
+
+def _fl_partner(M, N, row):
+    """the tile whose pair the single-row defects replace: the first tile of `row` whose planted offset is not zero (read as zeros,
+    such a tile's mean goes missing) and differs from that of row + 16 - any tile in a real launch; the pattern leaves one in
+    every row but those whose offsets all equal the other row's"""
+    _, o = fused_ln_pattern(M, N // 256)
+    return next(t for t in range(N // 256) if o[row, t] != 8 and o[row, t] != o[row + 16, t])
+
+
+def _fused_epilogue(z, gamma, beta, eps, dt, defect=None, row=FL_ROW, tile=1):
+    """z = dense + bias + residual [M, N] -> LayerNorm(z) gamma + beta [M, N], all arithmetic in `dt`"""
+    z, gamma, beta = z.to(dt), gamma.to(dt), beta.to(dt)
+    M, N = z.shape
+    ntn = N // 256
+    zt = z.view(M, ntn, 256)
+    mk = zt.sum(dim=2) / 256.0                                          # [M, ntn] per-tile mean
+    qk = (zt - mk[:, :, None]).square().sum(dim=2)                      # per-tile centred sum of squares
+    if defect == "partner pair from row + 16":
+        mk, qk = mk.clone(), qk.clone()
+        mk[row, tile], qk[row, tile] = mk[row + 16, tile], qk[row + 16, tile]
+    if defect == "partner pair read as zeros":
+        mk, qk = mk.clone(), qk.clone()
+        mk[row, tile] = qk[row, tile] = 0.0
+    msum = torch.zeros(M, dtype=dt)
+    for k in range(ntn):
+        msum = msum + mk[:, k]
+    mean = msum / float(ntn)
+    if defect == "mean over ntn - 1 tiles":
+        mean = mean.clone()
+        mean[row] = sum(mk[row, k] for k in range(ntn - 1)) / float(ntn - 1)
+    m2 = torch.zeros(M, dtype=dt)
+    for k in range(ntn):
+        d = mk[:, k] - mean
+        between = 256.0 * d * d
+        if defect == "between-tile term dropped":
+            between[row] = 0.0
+        m2 = m2 + (qk[:, k] + between)
+    rstd = 1.0 / torch.sqrt(m2 / float(N) + eps)
+    if defect == "last row with the statistics of the row before":
+        mean, rstd = mean.clone(), rstd.clone()
+        mean[M - 1], rstd[M - 1] = mean[M - 2], rstd[M - 2]
+    out = (z - mean[:, None]) * rstd[:, None] * gamma + beta
+    if defect == "slab with the gamma of the next 16 columns":
+        r0, c0 = 16 * (row // 16), 256 * tile + 64
+        out[r0:r0 + 16, c0:c0 + 64] = (z[r0:r0 + 16, c0:c0 + 64] - mean[r0:r0 + 16, None]) * rstd[r0:r0 + 16, None] \
+            * gamma[c0 + 16:c0 + 80] + beta[c0:c0 + 64]
+    return out
+
+
+FL_DEFECTS = ("between-tile term dropped", "partner pair from row + 16", "partner pair read as zeros", "mean over ntn - 1 tiles",
+              "last row with the statistics of the row before", "slab with the gamma of the next 16 columns")
+
+
+@functools.lru_cache(maxsize=None)
+def _fl_case(N, mode, planted):
+    x, w, b, res, gamma, beta = fused_ln_inputs(FL_M, N, FL_K, mode, 4000 + N, planted=planted, device="cpu")
+    z32 = x.float() @ w.float().T + b + res.float()                      # the fp32 accumulator + bias + residual
+    return z32, gamma, beta, fused_ln_ref64(x, w, b, res, gamma, beta, 1e-12)
+
+
+@pytest.mark.parametrize("mode", ["bf16", "fp16"])
+@pytest.mark.parametrize("N", [512, 1024, 4096])
+def test_fused_ln_gate_on_the_restated_epilogue(N, mode):
+    """96 rows, K = 64, planted residual.  Accepted at 1.0 x floor: the float64 reference rounded to the output grid, and the
+    fp32 restatement of the epilogue rounded once.  Rejected, each in ONE row (or one 16 x 64 slab) and at the block that holds it:
+    every defect of FL_DEFECTS."""
+    z32, gamma, beta, ref = _fl_case(N, mode, True)
+    tile = _fl_partner(FL_M, N, FL_ROW)
+    g = fused_ln_gate(round_to(ref, mode), ref, mode)
+    assert g.ok and g.worst == 1.0 and g.whole == 1.0, str(g)
+    assert rel_l2_t(_fused_epilogue(z32, gamma, beta, 1e-12, torch.float64), ref) < 1e-6      # (the operands' fp32 product only)
+    g = fused_ln_gate(_fused_epilogue(z32, gamma, beta, 1e-12, torch.float32).to(DT[mode]), ref, mode)
+    print(g)
+    assert g.ok and g.worst < 1.02 and g.whole < 1.01, str(g)
+    for name in FL_DEFECTS:
+        bad = _fused_epilogue(z32, gamma, beta, 1e-12, torch.float32, name, FL_ROW, tile).to(DT[mode])
+        g = fused_ln_gate(bad, ref, mode)
+        print(f"N {N} {mode} {name}: {g}")
+        assert not g.ok and g.worst > 3 * BWD_BLOCK, str(g)          # (the mildest: a tile of offset sigma / 2 read as zeros among 16, 6.5 x)
+        if "last row" in name:
+            assert g.where[0] == (FL_M - 1) // 4, str(g)
+        elif "slab" in name:
+            assert g.where[0] // 4 == FL_ROW // 16 and g.where[1] == tile, str(g)
+        else:
+            assert g.where[0] == FL_ROW // 4, str(g)
+
+
+def test_fused_ln_gate_needs_the_planted_rows():
+    """Why the inputs are planted.  One row in every block of 4 drops the between-tile term of the merge (the blocks are gated
+    independently: 24 single-row defects at once).  On plain N(0,1) operands the tile means of a row differ by sigma / 16 and nearly
+    every block passes the bf16 gate (measured: all of 24 at N = 512 and 4096, 23 at N = 1024, worst 1.60 x floor) - with a quarter
+    of all rows wrong the whole tensor reads 1.14 x floor at most, under the limit as well; on the planted rows every block is rejected, the mildest at 6.5 x floor."""
+    rows = torch.arange(1, FL_M, 4)
+    for N in (512, 1024, 4096):
+        ratios = {}
+        for planted in (False, True):
+            z32, gamma, beta, ref = _fl_case(N, "bf16", planted)
+            bad = _fused_epilogue(z32, gamma, beta, 1e-12, torch.float32, FL_DEFECTS[0], rows).to(torch.bfloat16)
+            ratio = (block_rel_l2(bad, ref, 4, 256) / block_rel_l2(round_to(ref, "bf16"), ref, 4, 256)).max(dim=1).values
+            g = fused_ln_gate(bad, ref, "bf16")
+            assert float(ratio.max()) == g.worst
+            print(f"N {N} planted {planted}: per block {float(ratio.min()):.2f} .. {float(ratio.max()):.2f} x floor, "
+                  f"{int((ratio <= BWD_BLOCK).sum())} of {ratio.numel()} pass; {g}")
+            ratios[planted] = (ratio, g)
+        assert float((ratios[False][0] <= BWD_BLOCK).float().mean()) >= 0.9 and ratios[False][1].whole < BWD_BLOCK, str(ratios[False][1])
+        assert float(ratios[True][0].min()) > 4 * BWD_BLOCK, str(ratios[True][1])
