@@ -192,7 +192,9 @@ int mavlm_step_batch_active(mavlm_ctx* ctx, const void* const* segs, int32_t n_a
  * the forward - the memory is the same bits with and without frame_scores and under every mavlm_set_frame_score_mode.  The
  * column sums of all videos use a scratch region of their own behind every other one (no offset of mavlm_workspace_layout moves).
  * Under autograd the same step is composed on the host from the stand-alone operators (BatchedProjector.step_train_frames): the
- * variable-length forward above, its backward mavlm_attention_bwd_batch_varlen and the variable-length column sums.
+ * variable-length forward above, its backward mavlm_attention_bwd_batch_varlen and the variable-length column sums; at
+ * head_dim 448 (behind the Python switch set_attention_hd_varlen_train, off by default) mavlm_attention_hd_batch_varlen, its
+ * backward mavlm_attention_bwd_hd_batch_varlen and one single-video column-sum pass per video.
  * MAVLM_E_ARG: n_active outside 1 .. B, n_active > 16 with unequal F, an F[b] outside its range, ld_scores too small;
  * MAVLM_E_STATE: a single-video context, a growing prefix, attention maps bound while the F differ. */
 int mavlm_step_batch_frames(mavlm_ctx* ctx, const void* const* segs, const int32_t* F, int32_t n_active, void* frame_scores,
@@ -576,6 +578,19 @@ int mavlm_attention_bwd_batch_varlen(const void* Q, int32_t ldq, const void* K, 
                                      int32_t lddq, void* dK, int32_t lddk, void* dV, int32_t lddv, int32_t R, const int32_t* S,
                                      const int64_t* kv_off, const int64_t* dkv_off, int32_t H, float scale, int32_t nb,
                                      int32_t head_dim, int32_t dtype, void* stream);
+/* The same for heads of 448 columns, the backward of mavlm_attention_hd_batch_varlen: parameters, layout, HOST arrays and the
+ * null-gradient rule as above.  dK and dV together run the fused dK + dV kernel, one alone its own kernel, as
+ * mavlm_attention_bwd_hd does.  Video b's rows of dQ / dK / dV carry, bit for bit, what mavlm_attention_bwd_hd gives on that
+ * video's operands alone; rows of dK / dV outside the videos' ranges are left untouched; no atomics, one owner per element.
+ * Checks before anything is enqueued, in this order: the MAVLM_E_ARG cases above that need no width (a null required pointer,
+ * nb outside 1..16, H % nb != 0, R < 1, a dtype other than 0 / 1); MAVLM_E_SHAPE for a head_dim other than 448; MAVLM_E_ARG for
+ * misaligned or too narrow operands (widths against (H / nb) * 448; dQ / dK / dV 8-byte aligned), S[b] < 1, offsets that are
+ * negative or no multiple of 8, overlapping ranges by any of the four strides, a video whose keys exceed the 32-bit offsets. */
+int mavlm_attention_bwd_hd_batch_varlen(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv,
+                                        const void* O, int32_t ldo, const void* dO, int32_t lddo, const float* lse2, float* delta,
+                                        void* dQ, int32_t lddq, void* dK, int32_t lddk, void* dV, int32_t lddv, int32_t R,
+                                        const int32_t* S, const int64_t* kv_off, const int64_t* dkv_off, int32_t H, float scale,
+                                        int32_t nb, int32_t head_dim, int32_t dtype, void* stream);
 /* C[M,N] 16-bit = A[M,K] . W[N,K]^T, contraction split over `splits` workgroup planes; ws = splits*M*N fp32;
  * zero_bias = N fp32 zeros.  For dW = dY^T X, whose contraction runs over all rows of the activations. */
 int mavlm_linear_splitk(const void* A, int32_t lda, const void* W, int32_t ldw, void* C, int32_t M, int32_t N, int32_t K,

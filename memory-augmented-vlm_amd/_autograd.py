@@ -128,7 +128,7 @@ class AttentionFn(torch.autograd.Function):
     zero-padded by the caller).  Saves O and the log-sum-exp; the backward recomputes the probabilities per tile.
     `nb` > 1: a row batch - q holds the query rows of nb videos one after the other, k / v are [nb, S, W] views (`heads` per
     video); forward and backward are ONE launch each over the (video, head) pairs, on the schedule of `mavlm_step_batch`.
-    `key_counts` (a tuple, heads of <= 128 columns): a variable-length row batch - video b has key_counts[b] keys, k / v are
+    `key_counts` (a tuple; head width 128 or 448, the latter through the `_hd` operators): a variable-length row batch - video b has key_counts[b] keys, k / v are
     [sum(key_counts), W] with the videos' keys packed back to back; the plain grid per video, forward and backward (`nb` is
     not read: the videos are counted by the tuple)."""
 
@@ -137,9 +137,12 @@ class AttentionFn(torch.autograd.Function):
         q, k, v = q.detach(), k.detach(), v.detach()
         ctx.key_counts = tuple(int(s) for s in key_counts) if key_counts is not None else None
         if key_counts is not None:
-            if head_dim != 128:
-                raise capi.MavlmError(f"variable-length attention: head width {head_dim} (heads of <= 128 columns only)")
-            o, lse = ops.attention_batch_varlen(q, k, v, heads, ctx.key_counts, want_lse=True, scale=scale)
+            if head_dim not in (128, 448):
+                raise capi.MavlmError(f"variable-length attention: head width {head_dim} (128 or 448)")
+            if head_dim == 448:
+                o, lse = ops.attention_hd_batch_varlen(q, k, v, heads, ctx.key_counts, want_lse=True, scale=scale)
+            else:
+                o, lse = ops.attention_batch_varlen(q, k, v, heads, ctx.key_counts, want_lse=True, scale=scale)
         elif nb > 1:
             o, lse = ops.attention_batch(q, k, v, heads, nb, want_lse=True, scale=scale, head_dim=head_dim)
         else:
@@ -153,7 +156,10 @@ class AttentionFn(torch.autograd.Function):
     def backward(ctx, do, _dlse):
         q, k, v, o, lse = ctx.saved_tensors
         n = ctx.needs_input_grad
-        if ctx.key_counts is not None:
+        if ctx.key_counts is not None and ctx.head_dim == 448:
+            dq, dk, dv = ops.attention_bwd_hd_batch_varlen(q, k, v, o, _c(do), lse, ctx.heads, ctx.key_counts, n[0], n[1], n[2],
+                                                           scale=ctx.scale)
+        elif ctx.key_counts is not None:
             dq, dk, dv = ops.attention_bwd_batch_varlen(q, k, v, o, _c(do), lse, ctx.heads, ctx.key_counts, n[0], n[1], n[2],
                                                         scale=ctx.scale)
         elif ctx.nb > 1:
@@ -220,7 +226,7 @@ def attention_block(attn, q_in, k, v, want_stats=False, patches_per_frame=196, n
     (padded-head layout; may be column views); returns (out, (q, k, lse) | None).  `nb` > 1: the stacked rows of nb videos
     and [nb, S, W] keys / values - every GEMM and LayerNorm runs once over all rows, the attention over (video, head) pairs.
     `key_counts`: the stacked rows of len(key_counts) videos and PACKED [sum(key_counts), W] keys / values, video b attending to
-    its own key_counts[b] rows (`AttentionFn`'s variable-length form; heads of <= 128 columns)."""
+    its own key_counts[b] rows (`AttentionFn`'s variable-length form; heads of <= 128 columns, or of 448)."""
     H = attn.num_attention_heads
     hd = attn.attention_head_size
     if hd > 128 and hd != 448:

@@ -175,6 +175,9 @@ SIGNATURES = {
     "mavlm_attention_bwd_batch_varlen": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32,
                                                    i32, C.POINTER(i32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32, C.c_float,
                                                    i32, i32, i32, vp]),
+    "mavlm_attention_bwd_hd_batch_varlen": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32,
+                                                      i32, C.POINTER(i32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32,
+                                                      C.c_float, i32, i32, i32, vp]),
     "mavlm_prof_enable": (C.c_int, [i32]),
     "mavlm_prof_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), i32]),

@@ -567,6 +567,66 @@ def attention_bwd_batch_varlen(q, k, v, o, do, lse2, heads, key_counts, need_dq=
     return dq, dk, dv
 
 
+def attention_bwd_hd_batch_varlen(q, k, v, o, do, lse2, heads, key_counts, need_dq=True, need_dk=True, need_dv=True, scale=None,
+                                  dk_out=None, dv_out=None):
+    """`attention_bwd_batch_varlen` for heads of 448 columns (`mavlm_attention_bwd_hd_batch_varlen`), the gradients of
+    `attention_hd_batch_varlen`: video b's rows equal `attention_bwd_hd` on its own operands bit for bit (dk and dv together run the
+    fused kernel, as there).  Operands, results and `dk_out` / `dv_out` as `attention_bwd_batch_varlen`, W = heads * 448."""
+    _need_gpu(q, k, v, o, do, lse2, dk_out, dv_out)
+    nb = len(key_counts)
+    RB, _, ldq = _rows(q)
+    ldk, offs = _kv_varlen(k, key_counts, "attention_bwd_hd_batch_varlen")
+    ldv, _ = _kv_varlen(v, key_counts, "attention_bwd_hd_batch_varlen")
+    _, _, ldo = _rows(o)
+    do = do if do.stride(-1) == 1 else do.contiguous()
+    _, _, lddo = _rows(do)
+    W = heads * 448
+    H = heads * nb
+    if RB % nb or ldv != ldk or k.shape[1] < W or v.shape[1] < W or o.shape != (RB, W) or do.shape != (RB, W) \
+            or lse2.shape != (H, RB // nb) or lse2.dtype != torch.float32 or not lse2.is_contiguous() or do.dtype != q.dtype \
+            or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise capi.MavlmError("attention_bwd_hd_batch_varlen: operand mismatch")
+    R, tot = RB // nb, k.shape[0]
+    dq = torch.empty((RB, W), device=q.device, dtype=q.dtype) if need_dq else None
+    dk = (dk_out if dk_out is not None else torch.empty((tot, W), device=q.device, dtype=q.dtype)) if need_dk else None
+    dv = (dv_out if dv_out is not None else torch.empty((tot, W), device=q.device, dtype=q.dtype)) if need_dv else None
+    lddk = lddv = W
+    doffs = [0] * nb
+    geo = [_kv_varlen(t, key_counts, "attention_bwd_hd_batch_varlen") for t in (dk, dv) if t is not None]
+    if geo:
+        if any(g[0] != geo[0][0] for g in geo) or any(t is not None and (t.shape[1] != W or t.dtype != q.dtype) for t in (dk, dv)):
+            raise capi.MavlmError("attention_bwd_hd_batch_varlen: dk / dv destinations must be [sum(key_counts), W] with one row stride")
+        lddk = lddv = geo[0][0]
+        doffs = geo[0][1]
+    delta = torch.empty((H, R), device=q.device, dtype=torch.float32)
+    p = lambda t: t.data_ptr() if t is not None else 0
+    capi.check(capi.lib().mavlm_attention_bwd_hd_batch_varlen(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(),
+                                                              ldo, do.data_ptr(), lddo, lse2.data_ptr(), delta.data_ptr(), p(dq), W,
+                                                              p(dk), lddk, p(dv), lddv, R, _i32s(key_counts), _i64s(offs),
+                                                              _i64s(doffs), H,
+                                                              1.0 / math.sqrt(448.0) if scale is None else float(scale), nb, 448,
+                                                              dtype_code(q.dtype), stream_ptr()),
+               "mavlm_attention_bwd_hd_batch_varlen")
+    return dq, dk, dv
+
+
+_HD_VARLEN_TRAIN = False
+
+
+def set_attention_hd_varlen_train(on):
+    """Switch of the TRAINING clip step (`step_train_frames`, `run_video_groups(train=True, clips_train=True)`) at heads of 448
+    columns, process-wide, OFF by default.  Off: clips of different frame counts are refused at that width and the grouping stays
+    the equal-length one.  On: the step runs `attention_hd_batch_varlen` / `attention_bwd_hd_batch_varlen` over the packed keys and
+    one single-video column-sum pass per video.  A Python switch: the training step is composed on the host, no C state."""
+    global _HD_VARLEN_TRAIN
+    _HD_VARLEN_TRAIN = bool(on)
+
+
+def attention_hd_varlen_train():
+    """What `set_attention_hd_varlen_train` was last given (False until then)."""
+    return _HD_VARLEN_TRAIN
+
+
 def transpose(x, pad_to=64, out_rows=None):
     """[rows, cols] 16-bit -> [cols, roundup(rows, 64)] with a zero-filled pad (the K-contiguous operand form of
     the contract-over-rows products).  `out_rows` > cols: the result gets that many rows, the extra ones zero (an

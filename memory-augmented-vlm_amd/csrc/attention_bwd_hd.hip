@@ -58,15 +58,29 @@ __device__ __forceinline__ void wait_lgkm() {
   else asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
 }
 
-template <typename T, int MODE, int HD>
+// Variable-length row batch (VL; every MODE - a call for dK and dV runs the fused MODE 3 at this width, so it has its form too):
+// video b has its own key count vl.S[b]; its keys start vl.off[b] elements into K / V and its key gradients vl.doff[b] elements
+// into dK / dV - the by-value arrays (scalar loads from the kernel-argument segment) replace the keys' row count and vb * kvb /
+// vb * okvb, as in attn_bwd_kernel<..., VL> (attention_bwd.hip).  The queries' side stays stacked, R rows per video.  Clamps,
+// descriptor ends, the key mask and the stores' bound all derive from that video's count, so video b's rows carry the bits of a
+// single-video launch over its operands, and keys packed back to back are never read or written across a video's end.  The
+// instantiations without VL take an empty argument.
+template <bool VL> struct attn_bwd_hd_vl_arg {};
+template <> struct attn_bwd_hd_vl_arg<true> { int S[MAVLM_VBASE_MAX]; long long off[MAVLM_VBASE_MAX]; long long doff[MAVLM_VBASE_MAX]; };
+
+__device__ __forceinline__ int vl_hd_count(const attn_bwd_hd_vl_arg<true>& vl, int vb) { return vl.S[vb]; }
+__device__ __forceinline__ int vl_hd_count(const attn_bwd_hd_vl_arg<false>&, int) { return 0; }
+
+template <typename T, int MODE, int HD, bool VL = false>
 __global__ __launch_bounds__(256, 1) void attn_bwd_hd_kernel(const uint16_t* __restrict__ X, int ldx,
                                                              const uint16_t* __restrict__ X2, int ldx2,
                                                              const uint16_t* __restrict__ Y, int ldy,
                                                              const uint16_t* __restrict__ Y2, int ldy2,
                                                              const float* __restrict__ lse2, const float* __restrict__ delta,
-                                                             uint16_t* __restrict__ Out, int ldo, int NX, int NY, int R, int H,
+                                                             uint16_t* __restrict__ Out, int ldo, int NX_, int NY_, int R, int H,
                                                              float c, float out_scale, uint16_t* __restrict__ Out2, int ldo2,
-                                                             int Hv, long long kvb, long long okvb) {
+                                                             int Hv, long long kvb, long long okvb,
+                                                             attn_bwd_hd_vl_arg<VL> vl = {}) {
   constexpr int NSUB = (HD + 127) / 128;
   constexpr int SUB = WKT * 256;                            // 8 KiB: [32 rows][256 B]
   constexpr int TILE = NSUB * SUB;                          // 32 KiB
@@ -91,11 +105,26 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_hd_kernel(const uint16_t* __r
   const int h = blockIdx.x % H;
   const int x0 = (blockIdx.x / H) * (32 * (4 / SL)) + grp * 32;
   const int r = lane & 31, hh = lane >> 5;
-  const int nt = (NY + WKT - 1) / WKT;
+  const int nt_ = (NY_ + WKT - 1) / WKT;
   // row batch (as attn_bwd_kernel): head h of the launch is head hc of video vb; every operand moves to that video's rows, so
   // that row indices, descriptor ends and 32-bit offsets stay those of ONE video.  (A single video: vb = 0, hc = h.)
   const int vb = h / Hv, hc = h - vb * Hv;
-  if (MODE == 0) {
+  // (VL: the launch passes the queries' R for both counts; the keys' side takes this video's)
+  const int NX = (VL && MODE != 0) ? vl_hd_count(vl, vb) : NX_, NY = (VL && MODE == 0) ? vl_hd_count(vl, vb) : NY_;
+  const int nt = (VL && MODE == 0) ? (NY + WKT - 1) / WKT : nt_;
+  if constexpr (VL) {
+    // dK / dV: the grid covers the longest video - a workgroup whose first stationary row lies at or past this video's last key
+    // leaves, all four waves alike (blockIdx and vb are workgroup-uniform), before the first LDS-DMA and the first barrier
+    if (MODE != 0 && (int)(blockIdx.x / H) * (32 * (4 / SL)) >= NX) return;
+    const long long kv0 = vl.off[vb], okv0 = vl.doff[vb];
+    if (MODE == 0) {
+      X += (size_t)vb * NX * ldx; X2 += (size_t)vb * NX * ldx2; Y += kv0; Y2 += kv0; Out += (size_t)vb * NX * ldo;
+    } else {
+      X += kv0; Y += (size_t)vb * NY * ldy; Y2 += (size_t)vb * NY * ldy2; Out += okv0;
+      if (MODE != 2) X2 += kv0;
+      if (MODE == 3) Out2 += okv0;
+    }
+  } else if (MODE == 0) {
     X += (size_t)vb * NX * ldx; X2 += (size_t)vb * NX * ldx2; Y += vb * kvb; Y2 += vb * kvb; Out += (size_t)vb * NX * ldo;
   } else {
     X += vb * kvb; Y += (size_t)vb * NY * ldy; Y2 += (size_t)vb * NY * ldy2; Out += vb * okvb;
@@ -439,7 +468,70 @@ hipError_t launch_all_hd(const mavlm_attn_bwd_args& a, int dtype, hipStream_t s)
   return hipGetLastError();
 }
 
+// Variable-length row batch: video b has a.vl_S[b] keys at a.vl_off[b] (K, V) and its key gradients at a.vl_doff[b] (dK, dV);
+// a.S, a.kv_bstride and a.dkv_bstride are not read.  Modes as launch_all_hd picks them (dK and dV together: the fused MODE 3).
+// dQ runs the grid of the equal-length row batch; dK / dV run the key blocks of the LONGEST video x all heads, and the
+// workgroups past a shorter video's last block leave at once.
+template <typename T, int HD>
+hipError_t launch_all_hd_vl(const mavlm_attn_bwd_args& a, int dtype, hipStream_t s) {
+  const int nb = a.nb;
+  if (!a.vl_S || !a.vl_off || !a.vl_doff || nb < 1 || nb > MAVLM_VBASE_MAX || a.H <= 0 || a.H % nb || a.R <= 0)
+    return hipErrorInvalidValue;
+  // the 32-bit buffer offsets of launch_all_hd (one tile past the end included), per video
+  const double lim = 2147483648.0;
+  if (((double)a.R + 64) * a.ldq * 2.0 >= lim || ((double)a.R + 64) * a.lddo * 2.0 >= lim) return hipErrorInvalidValue;
+  attn_bwd_hd_vl_arg<true> vl = {};
+  int smax = 0;
+  for (int b = 0; b < nb; ++b) {
+    const int S = a.vl_S[b];
+    if (S < 1 || a.vl_off[b] < 0 || a.vl_doff[b] < 0 || ((double)S + 64) * a.ldk * 2.0 >= lim || ((double)S + 64) * a.ldv * 2.0 >= lim)
+      return hipErrorInvalidValue;
+    vl.S[b] = S; vl.off[b] = a.vl_off[b]; vl.doff[b] = a.vl_doff[b];
+    smax = S > smax ? S : smax;
+  }
+  const float c = a.scale * 1.44269504088896340736f;
+  static mavlm_per_device_once once[4];
+  {
+    hipError_t e = once[0].dyn_lds((const void*)attn_bwd_hd_kernel<T, 0, HD, true>, bwd_hd_lds(HD));
+    if (e == hipSuccess) e = once[1].dyn_lds((const void*)attn_bwd_hd_kernel<T, 1, HD, true>, bwd_hd_lds(HD));
+    if (e == hipSuccess) e = once[2].dyn_lds((const void*)attn_bwd_hd_kernel<T, 2, HD, true>, bwd_hd_lds(HD));
+    if (e == hipSuccess) e = once[3].dyn_lds((const void*)attn_bwd_hd_kernel<T, 3, HD, true>, bwd_hd_lds(HD));
+    if (e != hipSuccess) return e;
+  }
+  const int Hv = a.H / nb;
+  for (int b = 0; b < nb; ++b) {          // delta [nb*Hv, R]: one pass per video over its R stacked rows (as launch_all_hd)
+    hipError_t e = mavlm_launch_rowdot((const uint16_t*)a.dO + (size_t)b * a.R * a.lddo, a.lddo,
+                                       (const uint16_t*)a.O + (size_t)b * a.R * a.ldo, a.ldo, a.delta + (size_t)b * Hv * a.R, a.R, Hv,
+                                       HD, dtype, s);
+    if (e != hipSuccess) return e;
+  }
+  const dim3 gq(((a.R + 63) / 64) * a.H), gk(((smax + 63) / 64) * a.H), gv(((smax + 127) / 128) * a.H);
+  auto launch = [&](auto kern, dim3 grid, const void* X, int ldx, const void* X2, int ldx2, const void* Y, int ldy, const void* Y2,
+                    int ldy2, void* out, int ldo, float out_scale, void* out2, int ldo2) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), bwd_hd_lds(HD), s, (const uint16_t*)X, ldx, (const uint16_t*)X2, ldx2,
+                       (const uint16_t*)Y, ldy, (const uint16_t*)Y2, ldy2, a.lse2, a.delta, (uint16_t*)out, ldo, a.R, a.R, a.R, a.H, c,
+                       out_scale, (uint16_t*)out2, ldo2, Hv, 0ll, 0ll, vl);
+  };
+  if (a.dQ != nullptr)
+    launch(attn_bwd_hd_kernel<T, 0, HD, true>, gq, a.Q, a.ldq, a.dO, a.lddo, a.K, a.ldk, a.V, a.ldv, a.dQ, a.lddq, a.scale, nullptr, 0);
+  if (a.dK != nullptr && a.dV != nullptr) {
+    launch(attn_bwd_hd_kernel<T, 3, HD, true>, gk, a.K, a.ldk, a.V, a.ldv, a.Q, a.ldq, a.dO, a.lddo, a.dK, a.lddk, a.scale, a.dV,
+           a.lddv);
+    return hipGetLastError();
+  }
+  if (a.dK != nullptr)
+    launch(attn_bwd_hd_kernel<T, 1, HD, true>, gk, a.K, a.ldk, a.V, a.ldv, a.Q, a.ldq, a.dO, a.lddo, a.dK, a.lddk, a.scale, nullptr, 0);
+  if (a.dV != nullptr)
+    launch(attn_bwd_hd_kernel<T, 2, HD, true>, gv, a.K, a.ldk, nullptr, 0, a.Q, a.ldq, a.dO, a.lddo, a.dV, a.lddv, 1.0f, nullptr, 0);
+  return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t mavlm_launch_attention_bwd_hd_varlen(const mavlm_attn_bwd_args& a, int head_dim, int dtype, hipStream_t s) {
+  if (head_dim != 448) return hipErrorInvalidValue;
+  return dtype == MAVLM_F16 ? launch_all_hd_vl<F16, 448>(a, dtype, s) : launch_all_hd_vl<BF16, 448>(a, dtype, s);
+}
 
 hipError_t mavlm_launch_attention_bwd_hd(const mavlm_attn_bwd_args& a, int head_dim, int dtype, hipStream_t s) {
   if (head_dim != 448) return hipErrorInvalidValue;

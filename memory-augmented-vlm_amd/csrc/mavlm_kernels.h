@@ -193,7 +193,7 @@ struct mavlm_attn_bwd_args {
   // keeps one owner: a batched launch gives the bits of nb single launches.  nb = 1: a single video.
   int nb = 1;
   long long kv_bstride = 0, dkv_bstride = 0;
-  // variable-length row batch (mavlm_launch_attention_bwd_varlen only): HOST arrays of nb <= MAVLM_VBASE_MAX entries - video b has
+  // variable-length row batch (mavlm_launch_attention_bwd_varlen / _hd_varlen only): HOST arrays of nb <= MAVLM_VBASE_MAX entries - video b has
   // vl_S[b] keys that start vl_off[b] elements into K and V, its key gradients vl_doff[b] elements into dK and dV; S and the two
   // strides are not read
   const int* vl_S = nullptr;
@@ -206,6 +206,9 @@ hipError_t mavlm_launch_attention_bwd_varlen(const mavlm_attn_bwd_args& a, int d
 extern int g_mavlm_attn_bwd_fused;      // attention_bwd.hip (mavlm_set_attention_bwd_fused)
 // the same for head_dim 448 (attention_bwd_hd.hip); O / dO / dQ / dK / dV are [rows, H*448]
 hipError_t mavlm_launch_attention_bwd_hd(const mavlm_attn_bwd_args& a, int head_dim, int dtype, hipStream_t s);
+// per-video key counts at head_dim 448 (a.vl_S / a.vl_off / a.vl_doff as mavlm_launch_attention_bwd_varlen reads them): dK and dV
+// together run the fused kernel, as above; video b's rows carry the bits of mavlm_launch_attention_bwd_hd on its operands alone
+hipError_t mavlm_launch_attention_bwd_hd_varlen(const mavlm_attn_bwd_args& a, int head_dim, int dtype, hipStream_t s);
 
 // backward.hip
 size_t mavlm_layernorm_bwd_partial_floats(int D);

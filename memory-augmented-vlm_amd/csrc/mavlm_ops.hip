@@ -578,6 +578,42 @@ int mavlm_attention_bwd_batch_varlen(const void* Q, int32_t ldq, const void* K, 
   return api_rc(mavlm_launch_attention_bwd_varlen(a, dtype, (hipStream_t)stream));
 }
 
+// the same at head columns of 448: dK and dV together run the fused kernel, as mavlm_attention_bwd_hd_batch does
+int mavlm_attention_bwd_hd_batch_varlen(const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv,
+                                        const void* O, int32_t ldo, const void* dO, int32_t lddo, const float* lse2, float* delta,
+                                        void* dQ, int32_t lddq, void* dK, int32_t lddk, void* dV, int32_t lddv, int32_t R,
+                                        const int32_t* S, const int64_t* kv_off, const int64_t* dkv_off, int32_t H, float scale,
+                                        int32_t nb, int32_t head_dim, int32_t dtype, void* stream) {
+  // every check comes before any launch
+  const bwd_abi p = {Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse2, delta, dQ, lddq, dK, lddk, dV, lddv};
+  if (bwd_abi_null(p) || R <= 0 || nb < 1 || nb > MAVLM_VBASE_MAX || H <= 0 || H % nb != 0 || (dtype != 0 && dtype != 1))
+    return MAVLM_E_ARG;
+  if (head_dim != 448) return MAVLM_E_SHAPE;
+  if (const int rc = bwd_abi_check(p, (H / nb) * 448)) return rc;
+  if (((uintptr_t)dQ | (uintptr_t)dK | (uintptr_t)dV) & 7) return MAVLM_E_ARG;
+  if (varlen_ranges_bad(S, kv_off, nb, ldk) || varlen_ranges_bad(S, kv_off, nb, ldv)) return MAVLM_E_ARG;
+  if ((dK && varlen_ranges_bad(S, dkv_off, nb, lddk)) || (dV && varlen_ranges_bad(S, dkv_off, nb, lddv))) return MAVLM_E_ARG;
+  const double lim = 2147483648.0;                          // the 32-bit buffer offsets of the kernel, per video
+  if (((double)R + 64) * ldq * 2.0 >= lim || ((double)R + 64) * lddo * 2.0 >= lim) return MAVLM_E_ARG;
+  long long off[MAVLM_VBASE_MAX], doff[MAVLM_VBASE_MAX];
+  double keys = 0.0;
+  int smax = 0;
+  for (int b = 0; b < nb; ++b) {
+    if (((double)S[b] + 64) * ldk * 2.0 >= lim || ((double)S[b] + 64) * ldv * 2.0 >= lim) return MAVLM_E_ARG;
+    off[b] = kv_off[b];
+    doff[b] = (dK || dV) ? dkv_off[b] : 0;
+    keys += S[b];
+    smax = S[b] > smax ? S[b] : smax;
+  }
+  mavlm_attn_bwd_args a = attn_bwd_args(p, R, smax, H, scale);
+  a.nb = nb; a.vl_S = S; a.vl_off = off; a.vl_doff = doff;
+  const int Hv = H / nb;
+  const double units = (dQ ? 3.0 : 0.0) + (dK ? 3.0 : 0.0) + (dV ? 2.0 : 0.0);
+  mavlm_prof_scope prof(MAVLM_K_ATTN_BWD, units * 2.0 * R * keys * Hv * 448, 2.0 * 448 * Hv * (4.0 * R * nb + 4.0 * keys),
+                        (hipStream_t)stream);
+  return api_rc(mavlm_launch_attention_bwd_hd_varlen(a, 448, dtype, (hipStream_t)stream));
+}
+
 int64_t mavlm_layernorm_bwd_ws_floats(int32_t D) { return (int64_t)mavlm_layernorm_bwd_partial_floats(D); }
 
 int mavlm_layernorm_bwd(const void* dy, const float* xin, const void* res, int32_t ldr, const float* gamma, void* dz,

@@ -535,8 +535,8 @@ def video_memory_tokens_clips_train(model, bp: BatchedProjector, images, frame_i
     `_train_block` builds every video's block (every frame of a clip is a fine frame).  Where that GEMM pair does not split its
     contraction the feature rows are the bits of the inference clip block.  The block is built from torch ops and the plain
     GEMMs: every hidden size the training path takes, 896 included (the inference clip emit needs a multiple of 256).  Heads of
-    448 columns have no variable-length attention: clips of different lengths are refused at that width
-    (`step_train_frames`).  Returns (list of [rows_b, D] blocks with grad in the caller's order, info as
+    448 columns: clips of different lengths are refused (`step_train_frames`) unless `ops.set_attention_hd_varlen_train(True)`
+    (off by default) - with it the step runs the variable-length 448 forward and backward.  Returns (list of [rows_b, D] blocks with grad in the caller's order, info as
     `video_memory_tokens_clips`)."""
     from .. import _autograd as ag
     layout_period(layout, images[0].shape[1])
@@ -831,9 +831,13 @@ def features_per_sample(video_of, tokens):
 
 
 def _narrow_heads(rm) -> bool:
-    """heads of at most 128 columns - the widths the variable-length attention serves (a model without layers: nothing to ask)"""
+    """heads of at most 128 columns - the widths the variable-length attention serves under autograd - or heads of 448 with
+    `ops.set_attention_hd_varlen_train(True)` (a model without layers: nothing to ask)"""
     layers = getattr(rm, "layers", None)
-    return not layers or layers[0].memory_segment_fusion_attention.attention_head_size <= 128
+    if not layers:
+        return True
+    hd = layers[0].memory_segment_fusion_attention.attention_head_size
+    return hd <= 128 or (hd == 448 and ops.attention_hd_varlen_train())
 
 
 def run_video_groups(model, videos, mem_prompt, frame_prompt, image_newline, with_frames=True, layout="one_token",
@@ -858,8 +862,9 @@ def run_video_groups(model, videos, mem_prompt, frame_prompt, image_newline, wit
     than 32 sampled frames are grouped by `plan_clip_batches` first - different frame counts in ONE step, one emit per group
     (`video_memory_tokens_clips`); every other video goes through the grouping above.
     `clips_train` (enable_clip_row_batches(on, training=True)): with `train` the clips are grouped by `plan_clip_batches` too
-    and a group runs through `video_memory_tokens_clips_train`; without `train` it changes nothing.  Heads of 448 columns
-    have no variable-length attention: at that width it changes nothing either - the grouping stays as it is today."""
+    and a group runs through `video_memory_tokens_clips_train`; without `train` it changes nothing.  Heads of 448 columns:
+    at that width it changes nothing either - the grouping stays the equal-length one - unless the process-wide switch
+    `ops.set_attention_hd_varlen_train(True)` (off by default) is set: then the clips are grouped by `plan_clip_batches` too."""
     rm = model.recurrent_memory_transformer
     if (clips and not train) or (clips_train and train and _narrow_heads(rm)):
         cgroups, rest = plan_clip_batches([v[0].shape[0] for v in videos], [(v[0].dtype, str(v[0].device)) for v in videos], sizes)
@@ -1411,8 +1416,9 @@ class LlavaMetaForCausalLM:
         `training=True` additionally groups the clips of a forward under autograd that way (off by default, also with `on`): a
         group takes one `BatchedProjector.step_train_frames` - the variable-length attention forward and backward - and
         `video_memory_tokens_clips_train` builds its blocks, at every hidden size of the training path (896 included).  Heads
-        of 448 columns have no variable-length attention backward: at that width the training grouping stays as it is with the switch
-        off.  `on=False` switches both off."""
+        of 448 columns: the training grouping stays as it is with the switch off unless `_ops.set_attention_hd_varlen_train(True)`
+        (process-wide, OFF by default; this method does not touch it) - then the step runs the variable-length 448 forward and its
+        backward `mavlm_attention_bwd_hd_batch_varlen`.  `on=False` switches both off."""
         self._clip_row_batches = bool(on)
         self._clip_row_batches_train = bool(on) and bool(training)
 

@@ -933,7 +933,9 @@ class BatchedProjector:
         (`ops.attention_bwd_batch_varlen`), and the frame scores come from ONE variable-length column-sum launch.  Returns a list
         of k detached [F_b] frame scores (None with `compute_frame_scores = False`); `frame_scores` gets one padded [k, Fmax]
         tensor (zeros behind a video's F_b).  Equal F_b take the launches and the bits of `step_train(ragged=True)`.  Heads of 448
-        columns have no variable-length kernel: different F_b at that width are refused before any launch.  No attention maps."""
+        columns: different F_b are refused before any launch unless `ops.set_attention_hd_varlen_train(True)` (off by default);
+        with it the layers run `ops.attention_hd_batch_varlen` / `ops.attention_bwd_hd_batch_varlen` and the frame scores come
+        from one single-video column-sum pass per video.  No attention maps."""
         return self._step_train("step_train_frames", segs, True, True)
 
     def _step_train(self, name, segs, ragged, frames):
@@ -949,10 +951,13 @@ class BatchedProjector:
             self._check_prefix(name if frames else "step_train(ragged=True)", k)
         elif k != B:
             raise capi.MavlmError(f"BatchedProjector.step_train: {B} chunks expected")
-        if frames and len({int(t.shape[0]) for t in segs if t.dim() == 3}) > 1 \
-                and proj.layers[0].memory_segment_fusion_attention.attention_head_size > 128:
+        hd0 = proj.layers[0].memory_segment_fusion_attention.attention_head_size
+        if frames and len({int(t.shape[0]) for t in segs if t.dim() == 3}) > 1 and hd0 > 128 \
+                and not (hd0 == 448 and ops.attention_hd_varlen_train()):
+            # (heads of 448 train through the variable-length `_hd` operators behind `ops.set_attention_hd_varlen_train`)
             raise capi.MavlmError("BatchedProjector.step_train_frames: chunks of different frame counts need the variable-length "
-                                  "attention, which heads of more than 128 columns (448) do not have")
+                                  "attention, which heads of more than 128 columns do not have (heads of 448: only with "
+                                  "ops.set_attention_hd_varlen_train(True), off by default)")
         Fs = self._check_chunks(name, segs, not frames, contiguous=False)
         F = Fs[0]
         varlen = len(set(Fs)) > 1                                   # else: the equal-length body, launch for launch
@@ -997,7 +1002,14 @@ class BatchedProjector:
                 q, kl, lse = stats
                 H, hd = atts[-1].num_attention_heads, atts[-1].attention_head_size
                 if varlen:
-                    part = ops.attention_colsum_batch_varlen(q, kl, lse, H, Sc, scale=ops.attn_scale(hd))
+                    if hd > 128:
+                        # heads of 448 have no variable-length column sums: the single-video operator per video, on row slices
+                        # of the packed operands (its bits by definition)
+                        pre = [sum(Sc[:b]) for b in range(k)]
+                        part = [ops.attention_colsum(q[b * R:(b + 1) * R], kl[pre[b]:pre[b] + Sc[b]], lse[b * H:(b + 1) * H], H,
+                                                     head_dim=hd, scale=ops.attn_scale(hd)) for b in range(k)]
+                    else:
+                        part = ops.attention_colsum_batch_varlen(q, kl, lse, H, Sc, scale=ops.attn_scale(hd))
                     scores = torch.zeros((k, max(Fs)), device=q.device, dtype=dt)
                     for b in range(k):
                         scores[b, :Fs[b]] = _frame_scores(part[b], Fs[b], P, dt)

@@ -12,7 +12,8 @@ CLIPS=31,27,23,19,16,12,9,5: clips of that many frames each (one chunk of all it
 round in this one process after warming up all three: as clip row batches (plan_clip_batches; a group takes ONE
 step_train_frames - the variable-length attention forward and backward -, what is left runs under the equal-length grouping),
 under the equal-length grouping alone (plan_row_batches over the frame counts: the switch off) and as single videos; ms per pass
-and per video, then the kernel table - launches per pass - of each (ROUNDS, default 5 here)."""
+and per video, then the kernel table - launches per pass - of each (ROUNDS, default 5 here).  HIDDEN=3584 (heads of 448): the clip
+leg runs with ops.set_attention_hd_varlen_train(True) (the variable-length 448 forward and backward), the other two with it off."""
 import ctypes, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -96,17 +97,23 @@ if os.environ.get("CLIPS"):
         rm.zero_grad(set_to_none=True)
         equal_groups(list(range(len(frames)))).backward()
     cgroups, rest = arch.plan_clip_batches(frames)
+    from memory_augmented_vlm_amd import _ops as ops
+    wide = HID // 8 == 448           # heads of 448: the clip leg needs ops.set_attention_hd_varlen_train (off by default, and in the other legs)
     def clips():
         rm.zero_grad(set_to_none=True)
         loss = 0.0
-        for size, g in cgroups:
-            bp = engine(size)
-            bp.reset()
-            bp.step_train_frames([vids[i] for i in g])
-            loss = loss + sum(loss_of(bp.memory_cache(b)) for b in range(len(g)))
-        if rest:
-            loss = loss + equal_groups(rest)
-        loss.backward()
+        ops.set_attention_hd_varlen_train(wide)
+        try:
+            for size, g in cgroups:
+                bp = engine(size)
+                bp.reset()
+                bp.step_train_frames([vids[i] for i in g])
+                loss = loss + sum(loss_of(bp.memory_cache(b)) for b in range(len(g)))
+            if rest:
+                loss = loss + equal_groups(rest)
+            loss.backward()
+        finally:
+            ops.set_attention_hd_varlen_train(False)
     fns = {"clips": clips, "grouped": grouped, "singles": singles}
     eq_b, eq_a = arch.plan_row_batches(frames)
     print(f"CLIPS={frames}  M={M} hidden={HID}; clip row batches {[[frames[i] for i in g] for _, g in cgroups]} on engines of "
